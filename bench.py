@@ -18,6 +18,10 @@ Multi-GPU (torchrun, one process per GPU): clip-parallel — every rank scores i
 own clips against the full keyword database; no data-path collective, only the
 timing barrier and a max-reduce of the elapsed time ("scaling": "weak").
 
+A plain run sets up, warms up, times the steps and prints the line.  --full adds everything that takes runs of
+its own beside the headline figure: the phase breakdown of one warm step, the fp32 audit of the last timed clip, the
+CPU baseline and the companion runs.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -39,8 +43,8 @@ import torch  # noqa: E402
 # shared setup, the non-headline modes and the companion runs live in benchlib/ (re-exported here: tests and tools
 # call bench.build_keyword_db, bench.calibrate_kws, ...)
 from benchlib.common import (OP_POSITIVE_FRAC, VARIANTS, _calibration_pairs, _init_dist, _probs,  # noqa: E402,F401
-                             _rank_device, build_keyword_db, calibrate_fp8_tier, calibrate_kws, keyword_hs,
-                             kws_hparams, log, rank_times, realistic_bias_shift)
+                             _rank_device, build_keyword_db, calibrate_fp8_tier, calibrate_kws, dump_outputs,
+                             keyword_hs, kws_hparams, log, rank_times, realistic_bias_shift)
 from benchlib.companions import companion_runs, config_runs, end_to_end_runs  # noqa: E402
 from benchlib.modes import run_api, run_longform, run_plumbing  # noqa: E402
 
@@ -250,7 +254,18 @@ def main():
                     help="setup: bias-correct the bf16 scoring network (KwsEngine.calibrate_bias) from the fp32 "
                          "network's conv-input means over the database's first N keywords vs a calibration clip that "
                          "is not timed (0.24 s at 512); 0 = the folded biases")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline measurement, run everything else the bench measures or checks: the phase "
+                         "breakdown of one warm step, the fp32 audit of the last timed clip, the CPU baseline and the "
+                         "companion runs (child processes); --no-audit / --no-cpu-baseline / --no-companions switch "
+                         "single parts of it off.  Without --full none of them runs; the breakdown step used to be one "
+                         "more warm pass before the timed steps, so a plain run warms up with exactly --warmup steps "
+                         "(with --warmup 0 every first-call cost falls into the timed steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (what a caller of the timed "
+                         "path receives) as DIR/<name>.npy, float32 / float64; the inputs are seeded, so two builds run "
+                         "with the same arguments can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--prof-dump", default=None,
                     help="write every timed conv launch (start/end ms from the hipEvents, algorithmic FLOPs) and the "
                          "timed region's CLOCK_MONOTONIC bounds to this JSON file, so the roofline's union-of-intervals "
@@ -263,7 +278,7 @@ def main():
                          "calibration pairs (or --fp8-band)")
     ap.add_argument("--fp8-band", type=float, default=None, help="fp8 tier band (default: calibrated)")
     ap.add_argument("--no-companions", dest="companions", action="store_false",
-                    help="skip the fp8-first companion runs (child processes after the headline measurement: the "
+                    help="--full: skip the fp8-first companion runs (child processes after the headline measurement: the "
                          "realistic operating point with and without --fp8-first, and --fp8-first at this point)")
     ap.add_argument("--operating-point", choices=["synthetic", "realistic", "sparse"], default="synthetic",
                     help="synthetic: the seeded classifier as is (probabilities straddle 0.5, ~1/3 of the keywords "
@@ -272,7 +287,7 @@ def main():
                          "keywords per clip: a keyword prompt short enough that the decoded transcript survives the "
                          "reference's outputs[:, len(prompt_ids):] slice, pba_whisper.py:338)")
     ap.add_argument("--no-audit", dest="audit", action="store_false",
-                    help="skip the post-run audit (every pair of the last timed clip re-scored in fp32 and compared "
+                    help="--full: skip the post-run audit (every pair of the last timed clip re-scored in fp32 and compared "
                          "with the timed step's decisions: audit_flips, audit_max_bf16_err, audit_band_margin)")
     ap.add_argument("--audit-pass", type=int, default=512,
                     help="audit: re-score the pairs in host-synchronised passes of this many pairs (0: one call, "
@@ -323,6 +338,8 @@ def main():
                          "as the step (gloo); measures nothing of the hot path")
     ap.add_argument("--plumbing-ms", type=float, default=20.0, help="--plumbing: rank r's step sleeps (r + 1) x this")
     args = ap.parse_args()
+    if args.plumbing and args.dump_outputs:
+        raise SystemExit("bench.py: --plumbing computes nothing, so there are no outputs for --dump-outputs")
     rc = launch_ranks(args.gpus, sys.argv[1:])
     if rc is not None:
         raise SystemExit(rc)
@@ -696,28 +713,30 @@ def main():
                                         idx.data_ptr(), nspot.data_ptr(), _lib.stream_handle()), "cbw_kws_spot")
 
     run_steps(0, args.warmup)
-    # phase breakdown on one warm step (torch events: libcbw launches on torch's current stream)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-    ev[0].record()
-    _, mel_pk = log_mel(clips[0], n_mel, packed=True)
-    ev[1].record()
-    enc.hidden_states(mel_pk, ids, normalize=True, out=hs)
-    ev[2].record()
-    pu, pum, pu32 = project_utt(hs)
-    ev[3].record()
-    lg_loc = logits[:db.shape[0]]   # this rank's keywords (the shard when keyword-sharded)
-    first_pass(pu[0], pum[0], lg_loc)
-    ev[4].record()
-    n_band = 0
-    if exact:
-        _, st = kws.score_exact(pu[0], pum[0], db, dbm, pu32, db32, args.threshold, band, chunk=args.chunk,
-                                logits_out=lg_loc, band_x3=x3_band, band_scaled=band_scaled, fp8_band=fp8_band)
-        n_band = st["band"]
-    ev[5].record()
-    torch.cuda.synchronize()
-    breakdown = {"mel": ev[0].elapsed_time(ev[1]), "encoder": ev[1].elapsed_time(ev[2]),
-                 "utt_projection": ev[2].elapsed_time(ev[3]), "kws_score": ev[3].elapsed_time(ev[4]),
-                 "kws_score_with_tiers_in_place": ev[4].elapsed_time(ev[5]), "band_pairs": n_band}
+    breakdown = None
+    if args.full or (sharded and not pipeline):   # (keyword-sharded without the pipeline: per_rank's scoring time)
+        # phase breakdown on one warm step (torch events: libcbw launches on torch's current stream)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        ev[0].record()
+        _, mel_pk = log_mel(clips[0], n_mel, packed=True)
+        ev[1].record()
+        enc.hidden_states(mel_pk, ids, normalize=True, out=hs)
+        ev[2].record()
+        pu, pum, pu32 = project_utt(hs)
+        ev[3].record()
+        lg_loc = logits[:db.shape[0]]   # this rank's keywords (the shard when keyword-sharded)
+        first_pass(pu[0], pum[0], lg_loc)
+        ev[4].record()
+        n_band = 0
+        if exact:
+            _, st = kws.score_exact(pu[0], pum[0], db, dbm, pu32, db32, args.threshold, band, chunk=args.chunk,
+                                    logits_out=lg_loc, band_x3=x3_band, band_scaled=band_scaled, fp8_band=fp8_band)
+            n_band = st["band"]
+        ev[5].record()
+        torch.cuda.synchronize()
+        breakdown = {"mel": ev[0].elapsed_time(ev[1]), "encoder": ev[1].elapsed_time(ev[2]),
+                     "utt_projection": ev[2].elapsed_time(ev[3]), "kws_score": ev[3].elapsed_time(ev[4]),
+                     "kws_score_with_tiers_in_place": ev[4].elapsed_time(ev[5]), "band_pairs": n_band}
 
     # conv launches per step: 53 per scoring chunk, and up to 53 per compensated-tier pass of 512 pairs
     n_conv_per_step = ((K_loc + args.chunk - 1) // args.chunk) * 53 + (53 * (K_loc // 512 + 2) if exact else 0)
@@ -782,6 +801,12 @@ def main():
     n_spotted = int(last_spot[1].item())
     # digest of the last clip's spotted index list (equal across scheduling modes: --x3-overlap / --no-x3-overlap)
     spot_digest = hashlib.sha1(last_spot[0][:n_spotted].cpu().numpy().tobytes()).hexdigest()[:16]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed clip's step handed back: every pair's final logits (after the re-scoring tiers; the
+        # gathered ones when keyword-sharded), the probabilities its spot computed from them and the spotted indices
+        dumped = dump_outputs(args.dump_outputs, {"logits": final_lg[0], "prob": prob,
+                                                  "spotted_indices": last_spot[0][:n_spotted]})
 
     def audit_last_clip():
         """After the timed region: every pair of the last timed clip (this rank's shard when keyword-sharded)
@@ -840,7 +865,7 @@ def main():
                 "audit_max_final_err": float(f"{v[4]:.3g}"), "audit_s": round(time.perf_counter() - t_a, 2),
                 **fp8_audit}
 
-    audit = audit_last_clip() if (exact and args.audit and last_utt[0] is not None) else None
+    audit = audit_last_clip() if (args.full and exact and args.audit and last_utt[0] is not None) else None
     per_rank = None
     if sharded:   # per-rank breakdown: the serial part of a step = step time - the rank's own scoring time
         # the rank's own scoring and re-scoring times, measured over the timed steps on their streams
@@ -878,7 +903,7 @@ def main():
                        "clip_pipeline": pipeline},
             "pairs_per_s": round(value * K, 1),
             "rank_elapsed_s": [round(x, 4) for x in rank_elapsed],
-            "breakdown_ms": {k: round(v, 3) for k, v in breakdown.items()},
+            **({"breakdown_ms": {k: round(v, 3) for k, v in breakdown.items()}} if breakdown else {}),
             "timed_ms_per_clip": {"first_scoring_pass": None if timed_ms["score"] is None else round(timed_ms["score"], 3),
                                   "rescoring_tiers_on_tier_stream": None if timed_ms["tiers"] is None
                                   else round(timed_ms["tiers"], 3),
@@ -902,6 +927,8 @@ def main():
         }
         if audit is not None:
             rec.update(audit)
+        if dumped is not None:
+            rec["dumped_outputs"] = dumped
         if per_rank is not None:
             rec["per_rank"] = per_rank
         if not args.no_profile and conv_n.value > 0:
@@ -936,13 +963,13 @@ def main():
             if iso:
                 rec["roofline"].update(iso)
         log(f"[bench] timed: {rec['value']} {rec['unit']}, {rec['ms_per_step']} ms per step")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("[bench] cpu baseline (bounded sample on the host cores)")
             try:
                 rec["cpu_baseline"] = cpu_baseline(enc_sd, kws_sd, kws_hp, synth.synth_clip(0), K, enc_cfg)
             except Exception as e:  # the GPU result stands on its own
                 rec["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.companions and args.mode == "clip" and not args.fp8_first \
+        if args.full and world == 1 and args.companions and args.mode == "clip" and not args.fp8_first \
                 and args.operating_point == "synthetic":
             rec["fp8_first_mode"] = companion_runs(args)
             rec["configs_companion"] = config_runs()

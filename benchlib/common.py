@@ -102,6 +102,41 @@ def rank_times(dist, elapsed: float, dev) -> tuple:
     return max(per), per
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files of one run together stay below this
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> dict:
+    """--dump-outputs: each named output (tensor or array) as ``dirpath/<name>.npy``.  Floating-point values are
+    written as float32 (float64 stays float64), integers and booleans as float64 (exact below 2^53).  Nothing is cut
+    while the outputs together fit DUMP_LIMIT_BYTES.  Otherwise the budget is handed out from the smallest output
+    up: an output no larger than an equal share of what is left is written whole, a larger one is cut to that
+    share, as a fixed sample: the elements at a seeded (0) sorted random choice of flat positions (1-D), the same
+    positions in every run.  Returns {name: shape written}, for a sample {name: {"sample": n, "of_shape": shape}}."""
+    os.makedirs(dirpath, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            a = (a.float() if a.is_floating_point() and a.dtype != torch.float64 else a).numpy()
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    left = DUMP_LIMIT_BYTES - 256 * len(conv)   # (256: room for each .npy header)
+    order = sorted(conv, key=lambda k: conv[k].nbytes)
+    written = {}
+    for i, name in enumerate(order):
+        a = conv[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            written[name] = {"sample": int(pos.size), "of_shape": list(a.shape)}
+            a = a.reshape(-1)[pos]
+        else:
+            written[name] = list(a.shape)
+        left -= a.nbytes
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return {name: written[name] for name in conv}
+
+
 def calibrate_kws(kws, enc, ids, n_mel: int, K: int, D: int, n_cal: int, dev):
     """Setup-time bias / logit-offset calibration of the bf16 scoring pass (KwsEngine.calibrate_bias):
     a clip outside the timed ones (id 999 999) against the database's first ``n_cal`` keywords, so every rank

@@ -18,7 +18,7 @@ def _child_bench(extra: list, timeout: int = 420, steps: int = 5, warmup: int = 
     import subprocess
     import threading
     cmd = [sys.executable, BENCH, "--steps", str(steps), "--warmup", str(warmup),
-           "--no-cpu-baseline", "--no-companions", *extra]
+           "--full", "--no-cpu-baseline", "--no-companions", *extra]   # --full: its audit and phase breakdown
     log(f"[bench] companion: {' '.join(extra)}")
     t0 = time.time()
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)

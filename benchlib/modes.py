@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from benchlib.common import (OP_POSITIVE_FRAC, _init_dist, _rank_device, build_keyword_db, calibrate_fp8_tier,
-                             calibrate_kws, keyword_hs, kws_hparams, log, rank_times, realistic_bias_shift)
+                             calibrate_kws, dump_outputs, keyword_hs, kws_hparams, log, rank_times,
+                             realistic_bias_shift)
 
 
 def run_plumbing(args):
@@ -139,6 +140,7 @@ def run_longform(args):
             self.spot_stream = torch.cuda.Stream(device=dev, priority=0) if prio else None
             self.stats = {"windows": 0, "tokens": 0, "spotted": 0, "spot_s": 0.0, "transcript_tokens": 0}
             self.digests = {}   # audio index -> sha1 of its transcript's token ids
+            self.tokens = {}    # audio index -> those token ids (--dump-outputs)
             self.error = None
             spot0 = self.cb.keyword_spotting
 
@@ -192,6 +194,7 @@ def run_longform(args):
                         self.stats["tokens"] += len(gen)
                         self.stats["transcript_tokens"] += len(self.last_ids)
                         self.digests[i] = hashlib.sha1(np.asarray(gen, dtype=np.int64).tobytes()).hexdigest()[:16]
+                        self.tokens[i] = gen
                     self.stream.synchronize()
                     return None
                 if len(feats) == 1:
@@ -208,6 +211,7 @@ def run_longform(args):
                     toks = [int(t) for s_ in res["segments"][b] for t in s_["tokens"].tolist()]
                     self.stats["tokens"] += len(toks)
                     self.digests[i] = hashlib.sha1(np.asarray(toks, dtype=np.int64).tobytes()).hexdigest()[:16]
+                    self.tokens[i] = toks
                 self.stream.synchronize()
             return res
 
@@ -277,6 +281,10 @@ def run_longform(args):
         dist.all_reduce(tot)
         stats["windows"], stats["tokens"] = int(tot[0]), int(tot[1])
     audio_s = sum(len(audios[u]) for u in timed) / 16000 * world
+    if args.dump_outputs and rank == 0:   # the transcripts of the last timed step's audios (this rank's), as token ids
+        last = range((args.warmup + args.steps - 1) * A * G, (args.warmup + args.steps) * A * G)
+        dump_outputs(args.dump_outputs, {f"tokens_audio{i}": np.asarray(t, dtype=np.int64)
+                                         for ln in lanes for i, t in ln.tokens.items() if i in last})
     if rank == 0 and e2e:
         clips = len(timed) * world
         rec = {"metric": f"utterances/sec end to end (30 s clips: {args.model} encoder hs -> CB-Whisper LEF spotting vs "
@@ -392,6 +400,8 @@ def run_api(args):
     elapsed = time.perf_counter() - t0
     spotted = torch.nonzero(last[0] >= args.threshold).flatten().to(torch.int32)
     digest = hashlib.sha1(spotted.cpu().numpy().tobytes()).hexdigest()[:16]
+    if args.dump_outputs:   # what test_step returned for the last timed clip
+        dump_outputs(args.dump_outputs, {"preds": last[0], "spotted_indices": spotted})
     rec = {"metric": "utterances/sec (30 s clips) via efficient_kws.model.KWSModel.test_step (drop-in API), "
                      "Whisper-large-v3 LEF 10k kw",
            "value": round(args.steps / elapsed, 4), "unit": "utterances/s", "n_gpus": 1, "steps": args.steps,

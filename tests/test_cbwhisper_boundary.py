@@ -12,7 +12,6 @@ import yaml
 
 from cbw import synth
 
-REF_YAML = "/root/reference/src/configs/cb-whisper-acl.yaml"
 PROMPT = dict(keyword_prompt_prepend="The topic of today's speech is, ah, ",
               keyword_prompt_append=". Okay, then I'll continue.", keyword_separator=", ")
 
@@ -84,15 +83,16 @@ def test_runner_requires_placeholders_and_builds(fx, tmp_path, capsys):
         runner.main(["fit", "--config", p])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference config not present")
-def test_reference_yaml_unchanged_with_overrides(fx):
-    """The published cb-whisper-acl.yaml itself, unchanged, with its placeholders (and the hub encoder name,
-    not reachable offline) given on the command line as LightningCLI would take them."""
+def test_placeholder_yaml_with_overrides(fx, tmp_path):
+    """A config with the published schema and its placeholders left in, the placeholders (and the encoder
+    checkpoint) given on the command line as LightningCLI would take them."""
     from cbw import cli
-    cfg = cli.load_config(REF_YAML, [f"--model.init_args.root={fx['acl']}", "--model.init_args.kw_type=tts",
-                                     f"--model.init_args.whisper_ckpt={fx['whisper']}",
-                                     f"--model.init_args.kws_ckpt={fx['kws_ckpt']}", "--model.init_args.prompt=true",
-                                     "--model.init_args.oracle=kws", f"--model.init_args.encoder_ckpt={fx['encoder']}"])
+    p = yaml_like_reference(str(tmp_path), fx, placeholders=True)
+    assert cli.placeholders(cli.load_config(p)["model"]) != []
+    cfg = cli.load_config(p, [f"--model.init_args.root={fx['acl']}", "--model.init_args.kw_type=tts",
+                              f"--model.init_args.whisper_ckpt={fx['whisper']}",
+                              f"--model.init_args.kws_ckpt={fx['kws_ckpt']}", "--model.init_args.prompt=true",
+                              "--model.init_args.oracle=kws", f"--model.init_args.encoder_ckpt={fx['encoder']}"])
     assert cli.placeholders(cfg["model"]) == []
     m = cli.build(cfg["model"])
     assert m.hparams.keyword_separator == ", " and m.hparams.keywords_per_group == 100

@@ -15,9 +15,11 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*flags, ranks=1):
+def run_bench(*flags, ranks=1, full=True):
+    """--full: the audit of the last timed clip (and the phase breakdown); its CPU baseline and companions stay off"""
     args = [os.path.join(REPO, "bench.py"), "--model", "small", "--keywords", "720", "--steps", "3",
-            "--warmup", "1", "--no-cpu-baseline", "--no-profile", "--no-companions", *flags]
+            "--warmup", "1", *(["--full"] if full else []), "--no-cpu-baseline", "--no-profile", "--no-companions",
+            *flags]
     env = dict(os.environ, PYTHONFAULTHANDLER="1")   # an abort in the subprocess prints every thread's Python stack
     if ranks > 1:   # the N-rank code path on the one GPU (gloo; RCCL refuses two ranks on one device)
         args = ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr",
@@ -113,3 +115,33 @@ def test_longform_fp8_first_transcribes_like_bf16_first():
     assert f8["config"]["fp8_first"]["fp8_band"] > 0 and b16["config"]["operating_point"]["name"] == "realistic"
     assert f8["transcript_digests"] == b16["transcript_digests"]
     assert f8["spotted_keywords_per_window"] == b16["spotted_keywords_per_window"]
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the bench only sets up, warms up and times its steps: the line carries the headline fields
+    and none of the audit / CPU baseline / companion / breakdown figures.  --dump-outputs writes what the last
+    timed clip's step handed back (every pair's logits, their probabilities, the spotted indices) as float32 /
+    float64 .npy files, consistent with each other and with the line's digest, and the same from run to run."""
+    import hashlib
+
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        r = run_bench("--steps", "2", "--dump-outputs", d, full=False)
+        assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["unit"] == "utterances/s" and r["dtype"] == "bf16"
+        assert r["higher_is_better"] is True and r["value"] == pytest.approx(1e3 / r["ms_per_step"], rel=1e-3)
+        for k in ("breakdown_ms", "audit_flips", "cpu_baseline", "fp8_first_mode", "configs_companion", "end_to_end_companion"):
+            assert k not in r, k
+        assert sorted(os.listdir(d)) == ["logits.npy", "prob.npy", "spotted_indices.npy"]
+        lg, pr, ix = (np.load(os.path.join(d, f + ".npy")) for f in ("logits", "prob", "spotted_indices"))
+        assert lg.dtype == np.float32 and lg.shape == (720, 2) and pr.dtype == np.float32 and pr.shape == (720,)
+        assert ix.dtype == np.float64 and ix.shape == (r["spotted_last_clip"],) and np.isfinite(lg).all()
+        assert r["dumped_outputs"] == {"logits": [720, 2], "prob": [720], "spotted_indices": [len(ix)]}
+        assert hashlib.sha1(ix.astype(np.int32).tobytes()).hexdigest()[:16] == r["spotted_digest"]
+        np.testing.assert_array_equal(ix, np.nonzero(pr >= 0.5)[0])
+        e = np.exp(lg.astype(np.float64) - lg.max(1, keepdims=True))
+        np.testing.assert_allclose(pr, e[:, 1] / e.sum(1), rtol=0, atol=1e-6)   # fp32 softmax of O(1) logits
+        outs.append((lg, pr, ix))
+    for x, y in zip(*outs):
+        np.testing.assert_array_equal(x, y)

@@ -172,22 +172,28 @@ def test_default_layer_ids():
     assert default_layer_ids(4) == [2, 3, 4]          # tiny: [10:22] empty -> hs[-3:]
 
 
-@pytest.mark.parametrize("cfg", ["eval-LEF-comp-acl.yaml", "eval-LE-comp-acl.yaml", "eval-L-comp-acl.yaml",
-                                 "train-LEF.yaml", "train-L.yaml"])
-def test_reference_yaml_builds_model(cfg):
-    """The reference's own YAML configs (read as text, this container only) build the
-    drop-in KWSModel through the same class_path/init_args as LightningCLI would."""
-    path = os.path.join("/root/reference/src/efficient_kws/configs", cfg)
-    if not os.path.exists(path):
-        pytest.skip("reference configs not present (GPU box)")
+@pytest.mark.parametrize("switches,expect", [
+    (dict(learn_features=True, proj_mlp=True, frames_conv=True), 2),
+    (dict(learn_features=True, proj_mlp=True, frames_conv=False), 1),
+    (dict(learn_features=False, proj_mlp=False, frames_conv=False), 0),
+    (dict(learn_features=True, proj_mlp=False, frames_conv=False), 0)], ids=["LEF", "LE", "L", "L-learn-features"])
+def test_variant_configs_build_model(tmp_path, switches, expect):
+    """A YAML config of each spotter variant (written here: class_path / init_args as LightningCLI takes them, with
+    placeholder values for the threshold and the checkpoint) builds the drop-in KWSModel of that variant."""
     import yaml
     from run_efficient_kws import build_model
     from cbw.kws import variant_of
-    m = build_model(yaml.safe_load(open(path)))
+    cfg = {"model": {"class_path": "efficient_kws.model.KWSModel",
+                     "init_args": {"n_layers": 3, "embedding_dim": 1280, "features_size": [150, 1500],
+                                   "proj_mlp_units": 64, "resnet_version": "resnet-50", "threshold": ["THRESHOLD"],
+                                   **switches}},
+           "ckpt_path": ["CKPT"]}
+    p = tmp_path / "variant.yaml"
+    p.write_text(yaml.safe_dump(cfg))
+    m = build_model(yaml.safe_load(open(p)))
     assert type(m).__name__ == "KWSModel"
     assert m.hparams.n_layers == 3
     assert tuple(m.hparams.features_size) == (150, 1500)
-    expect = {"LEF": 2, "LE": 1, "L": 0}[cfg.split("-")[1].split(".")[0]]
     assert variant_of(vars(m.hparams)) == expect
 
 

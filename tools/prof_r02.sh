@@ -1,5 +1,8 @@
 #!/bin/bash
-# Round-2 measurement session: the default bench (with the CPU baseline and the per-launch dump), then
+# Round-2 measurement session: the bench with the per-launch dump, then the profiled passes.  The `bench` step is now
+# the lean run (headline line and in-step roofline only): it no longer records the audit, the CPU baseline or the
+# companions.  For a record like profiles/*_bench_default.json call it with BENCH_ARGS=--full (the profiled passes
+# take BENCH_ARGS too; add --no-companions for them, as the sessions on record did).  The profiled passes:
 # rocprofv3 passes (a kernel trace + stats pass and two PMC passes) whose records are cut to the timed
 # region by the CLOCK_MONOTONIC bounds bench.py --prof-dump writes, and the roofline recomputed from them.  usage: tools/prof_r02.sh TAG [bench] [trace] [pmc]
 TAG=$1; shift
@@ -19,7 +22,7 @@ if [[ "$ARGS" == *" trace "* ]]; then
 fi
 if [[ "$ARGS" == *" pmc "* ]]; then
   for C in FETCH_SIZE WRITE_SIZE; do
-    # (the audit runs in host-synchronised passes, bench.py --audit-pass: ~19k dispatches enqueued in one call crash the
+    # (no audit runs in this pass unless BENCH_ARGS holds --full; then it runs in host-synchronised passes, bench.py --audit-pass: ~19k dispatches enqueued in one call crash the
     # profiled process under counter collection, DESIGN.md §5, profiles/r05b_pmc_f32_*)
     timeout -k 10 600 rocprofv3 --pmc $C -d gpurun_out/pmc_${TAG}_$C -o run --output-format csv -- python3 bench.py ${BA} --prof-dump gpurun_out/dump_${TAG}_$C.json > gpurun_out/pmc_${TAG}_$C.log 2>&1; s=$?
     echo "pmc $C=$s"; tail -2 gpurun_out/pmc_${TAG}_$C.log
