@@ -81,6 +81,7 @@ SIGNATURES = {
     "cbw_encoder_hs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64,
                                c_void_p]),
     "cbw_conv2d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p]),
+    "cbw_conv1x1_chain": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p]),
     "cbw_conv1x1_dual": (c_int, [c_void_p] * 6 + [c_int] * 10 + [c_void_p]),
     "cbw_gemm_splitk_factor": (c_int, [c_int, c_int, c_int]),
     "cbw_gemm": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_int64, c_void_p]),

@@ -142,6 +142,15 @@ hipError_t cbw_conv_ring(const ConvArgs& a, hipStream_t st);
 bool cbw_conv_stream_supported(const ConvArgs& a);
 bool cbw_conv_stream_wanted(const ConvArgs& a);
 hipError_t cbw_conv_stream(const ConvArgs& a, hipStream_t st);
+// the stage-2 identity junction in one launch (conv_stream.hip): a = the expand 128 -> 512 with its bf16 residual and
+// ReLU (y as cbw_conv_stream writes it), and t1 [M][128] = relu(y . wr^T + br), the next block's 1x1 reduce,
+// bit-identical to the two launches.  wr_packed: the reduce weights [128][512] in the kernel's fragment order
+// (cbw_conv_chain_pack, 128 KB).  red_cout: the reduce's output channels (128).  CBW_CS_CHAIN=0 disables the chain
+// per call (cbw_conv_chain_enabled); the grid obeys cbw_cs_grid_cus like cbw_conv_stream
+bool cbw_conv_chain_enabled();
+bool cbw_conv_chain_supported(const ConvArgs& a, int red_cout);
+hipError_t cbw_conv_chain_pack(const uint16_t* wr, uint16_t* packed, hipStream_t st);
+hipError_t cbw_conv_chain(const ConvArgs& a, const uint16_t* wr_packed, const float* br, void* t1, hipStream_t st);
 
 // fused ResNet-50 stage-1 identity bottleneck (bottleneck.hip): x, y NHWC bf16 [N][H][W][256];
 // wr [64][256], wm [64][3][3][64], we [256][64] bf16 (BN folded), biases f32

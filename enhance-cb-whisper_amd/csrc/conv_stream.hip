@@ -220,6 +220,174 @@ __global__ __launch_bounds__(WAVES * 64, 1) void conv_stream_kernel(ConvArgs a, 
     }
 }
 
+// Chained variant for the stage-2 identity junctions: block b's expand 128 -> 512 + bias + residual + ReLU -> Y,
+// and in the same pass block b + 1's reduce T1' = relu(Y . Wr^T + br) (512 -> 128), so Y is never re-read.
+// A step's epilogue leaves lane (fr, fq) with the bf16x8 `o` of channels 64 s + 32 h + 8 fq .. + 7 of pixel
+// 16 pf + fr for each half h: exactly the B fragment of k-step 2 s + h of the same MFMA (what load_rows loads
+// for a K 512 conv), so the reduce consumes `o` from registers: 8 MFMAs per pixel fragment per half into 8
+// running accumulators (the 128 reduce channels), k-steps 0 .. 15 ascending into one fp32 accumulator, bias
+// after, ReLU, RNE to bf16 -- the arithmetic of conv_stream_kernel<16, 8, 2, 1, 0>, which runs that reduce as
+// a launch of its own, so T1' is bit-identical to the two launches.
+// The expand weights stay stationary in LDS; the reduce weights (128 KB more) do not fit beside them, so the
+// A fragments of Wr are read from global memory (L2-resident: every wave of the chip reads the same 128 KB)
+// in the fragment order cbw_conv_chain_pack leaves them in: [k-step 16][fragment 8][lane 64] x 16 bytes, one
+// contiguous 1 KB per wave instruction.  The reduce's output channels are permuted like the expand's
+// (perm_row over each 64 channels), so T1' leaves in 16-byte stores as well.
+// Those reads are the kernel's cost beside its HBM bytes (128 KB per wave unit), so it runs 64-pixel units on 4 waves
+// (one per SIMD, accumulators in AGPRs): each Wr fragment feeds 4 pixel fragments.
+// K = 128, Cout = 512 in one slice, bf16 residual, ReLU; no row prefetch (registers).
+constexpr int CC_K = 128, CC_N = 512, CC_R = 128;   // expand K, expand Cout = reduce K, reduce Cout
+template <int WAVES, int RD, int PF>
+__global__ __launch_bounds__(WAVES * 64, 1) void conv_stream_chain_kernel(ConvArgs a, const bf16* __restrict__ wrp,
+                                                                          const float* __restrict__ br, void* t1) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int KS = CC_K / 32;
+    constexpr int PITCH = CC_K * 2;
+    constexpr int NSTEPS = CC_N / CS_NSTEP;
+    constexpr int RF = CC_R / 16;           // reduce output fragments
+    float* bias_s = (float*)(smem + CC_N * PITCH);
+    float* br_s = bias_s + CC_N;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    // ---- setup: expand weights + both biases -> LDS
+    const bf16* __restrict__ Wt = (const bf16*)a.w;
+    constexpr int CPR = CC_K / 8;
+    for (int e = tid; e < CC_N * CPR; e += WAVES * 64) {
+        const int r = e / CPR, c = e - r * CPR;
+        *(bf16x8*)(smem + cs_off(r, c, PITCH)) = *(const bf16x8*)(Wt + (int64_t)perm_row(r) * CC_K + c * 8);
+    }
+    for (int c = tid; c < CC_N; c += WAVES * 64) bias_s[c] = a.bias ? a.bias[c] : 0.f;
+    for (int c = tid; c < CC_R; c += WAVES * 64) br_s[c] = br ? br[c] : 0.f;
+    __syncthreads();
+
+    const int M = a.M;
+    const int units = (M + (PF * 16) - 1) / (PF * 16);
+    const cs_i32x4 xr = cs_rsrc(a.x, (uint32_t)((int64_t)M * CC_K * 2));
+    const cs_i32x4 rr = cs_rsrc(a.res, (uint32_t)((int64_t)M * a.res_ld * 2));
+    const cs_i32x4 yr = cs_rsrc(a.y, (uint32_t)((int64_t)M * a.y_ld * 2));
+    const cs_i32x4 tr = cs_rsrc(t1, (uint32_t)((int64_t)M * CC_R * 2));
+    const cs_i32x4 wr = cs_rsrc(wrp, (uint32_t)(CC_R * CC_N * 2));
+    constexpr int OOR = 0x7ffffff0;
+
+    const int ustride = gridDim.x * WAVES;
+    for (int u = blockIdx.x * WAVES + wid; u < units; u += ustride) {
+        int roff[PF], yoff[PF], toff[PF];
+        bf16x8 xf[PF][KS];
+#pragma unroll
+        for (int pf = 0; pf < PF; ++pf) {
+            const int p = u * (PF * 16) + pf * 16 + fr;
+            const bool ok = p < M;
+            const int xo = ok ? p * CC_K * 2 + fq * 16 : OOR;
+            roff[pf] = ok ? p * a.res_ld * 2 + fq * 16 : OOR;
+            yoff[pf] = ok ? p * a.y_ld * 2 + fq * 16 : OOR;
+            toff[pf] = ok ? p * CC_R * 2 + fq * 16 : OOR;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) xf[pf][ks] = __builtin_bit_cast(bf16x8, cs_load(xr, xo, ks * 64));
+        }
+        cs_i32x4 res[RD][PF][2];
+        auto load_res = [&](cs_i32x4 (&dst)[PF][2], int s) {
+#pragma unroll
+            for (int pf = 0; pf < PF; ++pf)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) dst[pf][h] = cs_load(rr, roff[pf], (s * CS_NSTEP + h * 32) * 2);
+        };
+#pragma unroll
+        for (int r = 0; r < RD; ++r) load_res(res[r], r);
+        // the reduce's A fragments of k-step kk = 2 s + h
+        auto load_wr = [&](cs_i32x4 (&dst)[RF], int kk) {
+#pragma unroll
+            for (int c = 0; c < RF; ++c) dst[c] = cs_load(wr, lane * 16, (kk * RF + c) * 1024);
+        };
+        f32x4 tacc[PF][RF];
+#pragma unroll
+        for (int pf = 0; pf < PF; ++pf)
+#pragma unroll
+            for (int c = 0; c < RF; ++c) tacc[pf][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // half 0's Wr fragments go out ahead of the expand MFMAs, half 1's ahead of half 0's epilogue
+        auto step = [&](cs_i32x4 (&rs)[PF][2], int s) {
+            cs_i32x4 wr0[RF], wr1[RF];
+            load_wr(wr0, 2 * s);
+            f32x4 acc[PF][4];
+#pragma unroll
+            for (int pf = 0; pf < PF; ++pf)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[pf][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                bf16x8 wf[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    wf[c] = *(const bf16x8*)(smem + cs_off(s * CS_NSTEP + c * 16 + fr, ks * 4 + fq, PITCH));
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+#pragma unroll
+                    for (int pf = 0; pf < PF; ++pf)
+                        acc[pf][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[c], xf[pf][ks], acc[pf][c], 0, 0, 0);
+            }
+            load_wr(wr1, 2 * s + 1);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int nl = s * CS_NSTEP + h * 32 + fq * 8;
+                const f32x4 bv0 = *(const f32x4*)(bias_s + nl), bv1 = *(const f32x4*)(bias_s + nl + 4);
+#pragma unroll
+                for (int pf = 0; pf < PF; ++pf) {
+                    float v[8];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        v[q] = acc[pf][2 * h][q] + bv0[q];
+                        v[4 + q] = acc[pf][2 * h + 1][q] + bv1[q];
+                    }
+                    const bf16x8 rv = __builtin_bit_cast(bf16x8, rs[pf][h]);
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) v[q] += bf2f(rv[q]);
+                    bf16x8 o;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) o[q] = f2bf(fmaxf(v[q], 0.f));
+                    cs_store(__builtin_bit_cast(cs_i32x4, o), yr, yoff[pf], (s * CS_NSTEP + h * 32) * 2);
+#pragma unroll
+                    for (int c = 0; c < RF; ++c)
+                        tacc[pf][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            __builtin_bit_cast(bf16x8, h ? wr1[c] : wr0[c]), o, tacc[pf][c], 0, 0, 0);
+                }
+            }
+            if (s + RD < NSTEPS) load_res(rs, s + RD);
+        };
+        for (int s = 0; s < NSTEPS; s += RD) {
+#pragma unroll
+            for (int r = 0; r < RD; ++r) step(res[r], s + r);
+        }
+        // ---- T1' epilogue: lane (fr, fq) holds channels 64 t + 32 h + 8 fq .. + 7 in fragments 4 t + 2 h, + 1
+#pragma unroll
+        for (int t = 0; t < CC_R / 64; ++t)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int nl = t * 64 + h * 32 + fq * 8;
+                const f32x4 bv0 = *(const f32x4*)(br_s + nl), bv1 = *(const f32x4*)(br_s + nl + 4);
+#pragma unroll
+                for (int pf = 0; pf < PF; ++pf) {
+                    bf16x8 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        o[q] = f2bf(fmaxf(tacc[pf][4 * t + 2 * h][q] + bv0[q], 0.f));
+                        o[4 + q] = f2bf(fmaxf(tacc[pf][4 * t + 2 * h + 1][q] + bv1[q], 0.f));
+                    }
+                    cs_store(__builtin_bit_cast(cs_i32x4, o), tr, toff[pf], (t * 64 + h * 32) * 2);
+                }
+            }
+    }
+}
+
+// Wr [128][512] row-major -> the chained kernel's fragment order: 16-byte chunk ((kk 8 + c) 64 + lane) holds
+// row perm_row(16 c + fr), k = 32 kk + 8 fq .. + 7 (lane = 16 fq + fr)
+__global__ void conv_chain_pack_kernel(const bf16* __restrict__ w, bf16* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;   // one 16-byte chunk each
+    if (e >= CC_R * CC_N / 8) return;
+    const int lane = e & 63, c = (e >> 6) & 7, kk = e >> 9;
+    const int fr = lane & 15, fq = lane >> 4;
+    *(bf16x8*)(out + (int64_t)e * 8) = *(const bf16x8*)(w + (int64_t)perm_row(16 * c + fr) * CC_N + kk * 32 + fq * 8);
+}
+
 int num_cus_cs() {   // the persistent grid; CBW_CS_CUS=N (A/B) sizes it for N CUs, leaving the rest to the other streams
     static int n = 0;
     if (n == 0) {
@@ -329,5 +497,37 @@ hipError_t cbw_conv_stream(const ConvArgs& a, hipStream_t st) {
             break;
     }
 #undef CS_LAUNCH
+    return hipGetLastError();
+}
+
+// ---- chained expand + next reduce (conv_stream_chain_kernel)
+bool cbw_conv_chain_enabled() {   // CBW_CS_CHAIN=0 keeps the two launches; read on every call (tests A/B in one process)
+    const char* e = getenv("CBW_CS_CHAIN");
+    return !e || atoi(e) != 0;
+}
+
+bool cbw_conv_chain_supported(const ConvArgs& a, int red_cout) {
+    if (!cbw_conv_stream_supported(a) || a.x2 || a.Cin != CC_K || a.Cout != CC_N || red_cout != CC_R) return false;
+    if (!a.res || a.flags != CBW_EPI_RELU || a.y_ld != CC_N) return false;
+    return slice_channels(a.Cout, a.Cin) == a.Cout;   // one weight slice
+}
+
+hipError_t cbw_conv_chain_pack(const uint16_t* wr, uint16_t* packed, hipStream_t st) {
+    hipLaunchKernelGGL(conv_chain_pack_kernel, dim3(CC_R * CC_N / 8 / 256), dim3(256), 0, st, (const bf16*)wr,
+                       (bf16*)packed);
+    return hipGetLastError();
+}
+
+hipError_t cbw_conv_chain(const ConvArgs& a, const uint16_t* wr_packed, const float* br, void* t1, hipStream_t st) {
+    if (!cbw_conv_chain_supported(a, CC_R) || !wr_packed || !t1) return hipErrorNotSupported;
+    const int cus = cbw_cs_grid_cus > 0 ? std::min(num_cus_cs(), cbw_cs_grid_cus) : num_cus_cs();
+    const int G = 8 * std::max(1, cus / 8);
+    const size_t lds = (size_t)CC_N * CC_K * 2 + (size_t)(CC_N + CC_R) * 4;
+    // 4 waves x 64-pixel units, 2 residual steps in flight (isolated, 834 LEF pairs, whole grid: 448-465 us against
+    // 365 + 214 us for the two launches; 8 waves x 32-pixel units read Wr twice as often: 565-588 us, and 516 us
+    // with 2 residual steps in flight, which spills; Wr row-major instead of fragment order: 750 us)
+    cbw_last_conv_kernel = "conv_stream_chain_kernel<4, 2, 4>";
+    hipLaunchKernelGGL((conv_stream_chain_kernel<4, 2, 4>), dim3(G), dim3(4 * 64), lds, st, a, (const bf16*)wr_packed, br,
+                       t1);
     return hipGetLastError();
 }

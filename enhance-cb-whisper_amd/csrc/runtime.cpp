@@ -220,6 +220,41 @@ int launch_conv(const ConvW& c, const void* x, int N, int H, int W, void* y, con
     return CBW_OK;
 }
 
+// Block b's identity expand (c2: t2 -> y with residual res and ReLU) and block b + 1's 1x1 reduce (r0: y -> t1n) as
+// one chained launch (cbw_conv_chain) when both convs run on the streaming kernel today and the shapes are the
+// chain's; *done = false leaves both launches to the caller.  One profile record: the two convs' FLOPs summed.
+int launch_chain(const ConvW& c2, const ConvW& r0, const DevBuf& r0_packed, const void* t2, int N, int H, int W, void* y,
+                 const void* res, void* t1n, const void* zero, hipStream_t st, Prof* prof, bool* done) {
+    *done = false;
+    if (!r0_packed.p || !res || !cbw_conv_chain_enabled()) return CBW_OK;
+    if (c2.k != 1 || c2.stride != 1 || c2.relu || r0.k != 1 || r0.stride != 1 || !r0.relu || r0.cin != c2.cout)
+        return CBW_OK;
+    ConvArgs a{};
+    a.x = t2; a.w = c2.w.p; a.bias = c2.b.as<float>(); a.res = res; a.y = y; a.zero = zero;
+    a.N = N; a.H = a.Ho = H; a.W = a.Wo = W; a.Cin = c2.cin; a.Cout = c2.cout; a.KH = a.KW = 1;
+    a.sh = a.sw = 1;
+    a.M = N * H * W;
+    a.res_ld = a.y_ld = c2.cout;
+    a.flags = CBW_EPI_RELU;
+    ConvArgs r = a;   // the reduce as its own launch would see it
+    r.x = y; r.w = r0.w.p; r.bias = r0.b.as<float>(); r.res = nullptr; r.y = t1n;
+    r.Cin = r0.cin; r.Cout = r0.cout; r.res_ld = r.y_ld = r0.cout;
+    if (!cbw_conv_stream_wanted(a) || !cbw_conv_stream_wanted(r) || !cbw_conv_chain_supported(a, r0.cout)) return CBW_OK;
+    const bool rec = prof && prof->on && (size_t)(2 * prof->used + 1) < prof->ev.size();
+    if (rec) HIPCHK(hipEventRecord(prof->ev[2 * prof->used], st));
+    cbw_last_conv_kernel = "?";
+    HIPCHK(cbw_conv_chain(a, r0_packed.as<uint16_t>(), r0.b.as<float>(), t1n, st));
+    if (rec) {
+        HIPCHK(hipEventRecord(prof->ev[2 * prof->used + 1], st));
+        prof->flop[prof->used] = 2.0 * a.M * a.Cout * (double)a.Cin + 2.0 * a.M * r0.cout * (double)r0.cin;
+        prof->tier[prof->used] = prof->cur_tier;
+        prof->kern[prof->used] = cbw_last_conv_kernel;
+        prof->used++;
+    }
+    *done = true;
+    return CBW_OK;
+}
+
 size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ------------------------------------------------------------------ ResNet topology
@@ -233,6 +268,8 @@ struct BlockW {
     bool has_sc = false;
     bool fused_sc = false;   // shortcut folded into conv[2] as a second K-source (bottleneck)
     ConvW sc;
+    DevBuf chain_w;          // conv[0]'s weights in cbw_conv_chain's fragment order (stage-2 identity blocks: the
+                             // previous block's expand launch computes this block's reduce too)
     std::string prefix;      // parameter prefix of the block (bias correction re-folds from it)
     int stage = 0;           // 1..4
 };
@@ -524,6 +561,11 @@ int build_resnet(cbw_kws* h) {
                     } else {
                         CHK(load_conv_bn(h->ps, p + ".layer." + std::to_string(j), b.conv[j]));
                     }
+                }
+                if (!b.has_sc && cin == 512 && mid == 128) {   // the weights never change after this (bias
+                    CHK(b.chain_w.alloc((size_t)mid * cin * 2));   // calibration rewrites biases only)
+                    HIPCHK(cbw_conv_chain_pack(b.conv[0].w.as<uint16_t>(), b.chain_w.as<uint16_t>(), nullptr));
+                    HIPCHK(hipStreamSynchronize(nullptr));
                 }
             } else {
                 b.nconv = 2;
@@ -920,12 +962,16 @@ namespace {
 // workspace slot i % n.  begin(): the side streams wait for work already queued on the caller's
 // stream (inputs); end(): the caller's stream waits for every side stream, so completion on the
 // caller's stream means every chunk is done.
-// With several streams the streaming 1x1 convs (HBM-bound) size their persistent grid for 96 of the 256 CUs, leaving
-// the rest to the other streams' MFMA-bound convs (CBW_CS_SHARED_CUS, default 96; 0 = the whole chip): 6.16 vs 6.10
-// utt/s in the bench (r06l, profiles/r06l_cs_cus_ab.txt).
+// With several streams the streaming 1x1 convs (HBM-bound) size their persistent grid for 3/8 of the CUs (96 of 256),
+// leaving the rest to the other streams' MFMA-bound convs (CBW_CS_SHARED_CUS overrides; 0 = the whole chip): 6.16 vs
+// 6.10 utt/s in the bench (r06l, profiles/r06l_cs_cus_ab.txt).
 int cs_shared_cus() {
     const char* e = getenv("CBW_CS_SHARED_CUS");
-    return e ? atoi(e) : 96;
+    if (e) return atoi(e);
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    return n * 3 / 8;
 }
 struct ChunkStreams {
     cbw_kws* h;
@@ -1003,6 +1049,7 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
     auto blocks = [&](size_t b0, size_t b1, int n0, int nn, uint16_t*& x, uint16_t*& y, int& H, int& W,
                       int& C) -> int {
         auto at = [&](uint16_t* base, int hh, int ww, int cc) { return base + (size_t)n0 * hh * ww * cc; };
+        bool t1_ready = false;   // the previous block's chained expand launch already wrote this block's T1
         for (size_t bi = b0; bi < b1; ++bi) {
             const auto& b = h->blocks[bi];
             uint16_t* xo = at(x, H, W, C);
@@ -1051,9 +1098,18 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
                 uint16_t* t1 = at(T1, h1, w1, c0.cout);
                 uint16_t* t2 = at(T2, Ho, Wo, c1.cout);
                 uint16_t* yo = at(y, Ho, Wo, c2.cout);
-                CHK(launch_conv(c0, xo, nn, H, W, t1, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
+                if (!t1_ready) CHK(launch_conv(c0, xo, nn, H, W, t1, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
                 CHK(launch_conv(c1, t1, nn, h1, w1, t2, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
-                if (b.fused_sc) {   // y = relu([T2 | x strided] . [W_expand ; W_shortcut] + b): no shortcut tensor
+                // identity block followed by an identity block whose reduce qualifies (ResNet-50 s2b1 -> s2b2 -> s2b3):
+                // T1 is free here (c1 above consumed it earlier on this stream) and takes the next block's reduce
+                t1_ready = false;
+                if (!b.has_sc && bi + 1 < b1 && h->blocks[bi + 1].nconv == 3 && !h->blocks[bi + 1].has_sc) {
+                    const auto& nb = h->blocks[bi + 1];
+                    CHK(launch_chain(c2, nb.conv[0], nb.chain_w, t2, nn, Ho, Wo, yo, res, at(T1, Ho, Wo, nb.conv[0].cout),
+                                     h->zero.p, st, &h->prof, &t1_ready));
+                }
+                if (t1_ready) {   // y and the next T1 are written
+                } else if (b.fused_sc) {   // y = relu([T2 | x strided] . [W_expand ; W_shortcut] + b): no shortcut tensor
                     const Src2 s2{xo, b.sc.cin, H, W, b.sc.stride};
                     CHK(launch_conv(c2, t2, nn, Ho, Wo, yo, nullptr, CBW_EPI_RELU, h->zero.p, st, nullptr, nullptr,
                                     &h->prof, &s2));
@@ -2856,6 +2912,28 @@ int cbw_conv2d(const uint16_t* x, const uint16_t* w, const float* bias, const vo
     a.res_ld = a.y_ld = Cout;
     a.flags = flags;
     HIPCHK(cbw_conv_igemm(a, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_conv1x1_chain(const uint16_t* x, const uint16_t* we, const float* be, const uint16_t* res, const uint16_t* wr,
+                      const float* br, uint16_t* y, uint16_t* t1, int N, int H, int W, cbw_stream_t stream) {
+    if (!x || !we || !be || !res || !wr || !br || !y || !t1 || N <= 0 || H <= 0 || W <= 0)
+        return fail(CBW_ERR_INVALID, "cbw_conv1x1_chain: bad argument");
+    const void* zp = nullptr;
+    CHK(block_zero_page(&zp));
+    ConvArgs a{};
+    a.x = x; a.w = we; a.bias = be; a.res = res; a.y = y; a.zero = zp;
+    a.N = N; a.H = a.Ho = H; a.W = a.Wo = W; a.Cin = 128; a.Cout = 512; a.KH = a.KW = 1;
+    a.sh = a.sw = 1;
+    a.M = N * H * W;
+    a.res_ld = a.y_ld = 512;
+    a.flags = CBW_EPI_RELU;
+    if (!cbw_conv_chain_supported(a, 128)) return fail(CBW_ERR_INVALID, "cbw_conv1x1_chain: shape not supported");
+    DevBuf packed;   // a handle packs once at finalize; here per call, freed after the launch has finished
+    CHK(packed.alloc((size_t)128 * 512 * 2));
+    HIPCHK(cbw_conv_chain_pack(wr, packed.as<uint16_t>(), (hipStream_t)stream));
+    HIPCHK(cbw_conv_chain(a, packed.as<uint16_t>(), br, t1, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     return CBW_OK;
 }
 

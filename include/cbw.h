@@ -328,6 +328,12 @@ int cbw_beam_select(const float* lp, const int32_t* idx, int B, int k, int eos, 
  * flags: 1 ReLU, 2 GELU, 4 res is f32, 8 y is f32, 16 add res after the activation. */
 int cbw_conv2d(const uint16_t* x, const uint16_t* w, const float* bias, const void* res, void* y, int N, int H, int W,
                int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw, int flags, cbw_stream_t stream);
+/* One stage-2 identity junction of ResNet-50 as the scoring pass launches it (building block for the tests): block
+ * b's expand y = relu(x . we^T + be + res) (x [N][H][W][128], we [512][128], res / y [N][H][W][512]) and, from the
+ * same pass, block b + 1's reduce t1 = relu(y . wr^T + br) (wr [128][512], t1 [N][H][W][128]); both bit-identical to
+ * two cbw_conv2d calls.  Packs wr per call and returns after the launch has finished. */
+int cbw_conv1x1_chain(const uint16_t* x, const uint16_t* we, const float* be, const uint16_t* res, const uint16_t* wr,
+                      const float* br, uint16_t* y, uint16_t* t1, int N, int H, int W, cbw_stream_t stream);
 /* the fp8 tier's conv (building block, exposed for the parity tests): x e4m3 NHWC [N][H][W][Cin], w e4m3
  * [Cout][k][k][Cin], y[m][n] = act(alpha[n] * sum x.w + bias[n] (+ res[m][n] * res_scale)) stored as e4m3 of
  * y / y_scale (saturated at 448) or bf16 (out_bf16); res e4m3 [M][Cout] or NULL; pad k / 2; k 1 or 3;
