@@ -414,6 +414,89 @@ class KwsEngine:
                                               ws.data_ptr(), ws.numel(), _lib.stream_handle()), "cbw_kws_score")
         return (logits, feats) if features else logits
 
+    def _check_batch(self, utt, utt_mask, kwd, kwd_mask):
+        """Shape / dtype checks of ``score`` for a batch of utterances: utt bf16 [B, L, Tu, E]."""
+        if utt.dim() != 4 or kwd.dim() != 4:
+            raise ValueError(f"expected utt [B, L, Tu, E] and kwd [K, L, Tk, E], got {tuple(utt.shape)} "
+                             f"{tuple(kwd.shape)}")
+        K, L, Tk, E = kwd.shape
+        B, _, Tu, _ = utt.shape
+        if B < 1 or L != self.n_layers or E != self.feat_dim or tuple(utt.shape) != (B, L, Tu, E):
+            raise ValueError(f"shape mismatch: kwd {tuple(kwd.shape)} utt {tuple(utt.shape)}")
+        if utt.dtype != torch.bfloat16 or kwd.dtype != torch.bfloat16:
+            raise ValueError("projected features must be bf16 (use KwsEngine.project)")
+        if tuple(kwd_mask.shape) != (K, L, Tk) or tuple(utt_mask.shape) != (B, L, Tu):
+            raise ValueError(f"mask shapes {tuple(kwd_mask.shape)} {tuple(utt_mask.shape)} for kwd {tuple(kwd.shape)} "
+                             f"utt {tuple(utt.shape)}")
+        return (utt.contiguous(), utt_mask.to(torch.float32).contiguous(), kwd.contiguous(),
+                kwd_mask.to(torch.float32).contiguous())
+
+    def _pair_index(self, idx, n: int, trusted: bool, what: str) -> torch.Tensor:
+        if torch.is_tensor(idx):
+            if idx.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{what} must hold integers, got {idx.dtype}")
+        else:
+            idx = torch.as_tensor(np.asarray(idx, dtype=np.int64).reshape(-1))
+        idx = idx.reshape(-1)
+        if not trusted and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise ValueError(f"{what} out of range [0, {n})")
+        return idx.to(self.device, torch.int32).contiguous()
+
+    def score_pairs(self, utt: torch.Tensor, utt_mask: torch.Tensor, kwd: torch.Tensor, kwd_mask: torch.Tensor,
+                    pair_utt, pair_kwd, chunk: Optional[int] = None, features: bool = False,
+                    logits_out: Optional[torch.Tensor] = None, trusted: bool = False):
+        """A list of (utterance, keyword) pairs in one pass (cbw_kws_score_pairs): utt bf16 [B, L, Tu, E], utt_mask
+        f32 [B, L, Tu], kwd / kwd_mask as ``score``; pair p = (pair_utt[p], pair_kwd[p]), host sequences or device
+        integer tensors of one length P  ->  logits f32 [P, 2] in pair order (+ features f32 [P, L, Tk, Tu]).
+        The index ranges are checked before any launch (one host read-back for device tensors) unless ``trusted``."""
+        utt, utt_mask, kwd, kwd_mask = self._check_batch(utt, utt_mask, kwd, kwd_mask)
+        K, L, Tk, _ = kwd.shape
+        B, _, Tu, _ = utt.shape
+        pu = self._pair_index(pair_utt, B, trusted, "pair_utt")
+        pk = self._pair_index(pair_kwd, K, trusted, "pair_kwd")
+        P = pu.numel()
+        if pk.numel() != P:
+            raise ValueError(f"pair_utt has {P} entries, pair_kwd {pk.numel()}")
+        if P > 0 and K < 1:
+            raise ValueError("pairs given but no keywords")
+        if logits_out is not None and (tuple(logits_out.shape) != (P, 2) or logits_out.dtype != torch.float32
+                                       or not logits_out.is_contiguous()):
+            raise ValueError(f"logits_out must be contiguous f32 [{P}, 2], got {tuple(logits_out.shape)}")
+        logits = logits_out if logits_out is not None else torch.empty((P, 2), dtype=torch.float32, device=self.device)
+        feats = torch.empty((P, L, Tk, Tu), dtype=torch.float32, device=self.device) if features else None
+        if P > 0:
+            chunk = chunk or self.default_chunk(Tk, Tu)
+            with torch.cuda.device(self.device):
+                ws = self.workspace(Tk, Tu, chunk)
+                _lib.check(self.lib.cbw_kws_score_pairs(
+                    self.h, utt.data_ptr(), utt_mask.data_ptr(), B, kwd.data_ptr(), kwd_mask.data_ptr(), K, Tk, Tu,
+                    pu.data_ptr(), pk.data_ptr(), P, logits.data_ptr(), _lib.ptr(feats), chunk, ws.data_ptr(),
+                    ws.numel(), _lib.stream_handle()), "cbw_kws_score_pairs")
+        return (logits, feats) if features else logits
+
+    def score_batch(self, utt: torch.Tensor, utt_mask: torch.Tensor, kwd: torch.Tensor, kwd_mask: torch.Tensor,
+                    chunk: Optional[int] = None, logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every utterance of a batch against every keyword in one pass (cbw_kws_score_pairs without index arrays:
+        chunks of pairs may span utterances): utt bf16 [B, L, Tu, E], utt_mask f32 [B, L, Tu]  ->  logits f32
+        [B, K, 2], row b what ``score`` gives for utterance b."""
+        utt, utt_mask, kwd, kwd_mask = self._check_batch(utt, utt_mask, kwd, kwd_mask)
+        K, L, Tk, _ = kwd.shape
+        B, _, Tu, _ = utt.shape
+        if logits_out is not None and (tuple(logits_out.shape) != (B, K, 2) or logits_out.dtype != torch.float32
+                                       or not logits_out.is_contiguous()):
+            raise ValueError(f"logits_out must be contiguous f32 [{B}, {K}, 2], got {tuple(logits_out.shape)}")
+        logits = (logits_out if logits_out is not None
+                  else torch.empty((B, K, 2), dtype=torch.float32, device=self.device))
+        if K > 0:
+            chunk = chunk or self.default_chunk(Tk, Tu)
+            with torch.cuda.device(self.device):
+                ws = self.workspace(Tk, Tu, chunk)
+                _lib.check(self.lib.cbw_kws_score_pairs(
+                    self.h, utt.data_ptr(), utt_mask.data_ptr(), B, kwd.data_ptr(), kwd_mask.data_ptr(), K, Tk, Tu,
+                    None, None, B * K, logits.data_ptr(), None, chunk, ws.data_ptr(), ws.numel(),
+                    _lib.stream_handle()), "cbw_kws_score_pairs")
+        return logits
+
     def classify(self, maps: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
         """Resnet.forward (resnet.py:51-58) on NCHW f32 maps [K, L, H, W] -> logits [K, 2]."""
         maps = maps.to(self.device, torch.float32).contiguous()

@@ -187,6 +187,12 @@ hipError_t cbw_lef_time_project(const float* x, const float* w, const float* b, 
 // kwd: bf16 [K][L][Tk][E] normalised; utt: bf16 [L][Tu][E] normalised; masks f32.
 hipError_t cbw_sim_maps(const uint16_t* kwd, const float* kwd_mask, const uint16_t* utt, const float* utt_mask,
                         uint16_t* out, int K, int L, int Tk, int Tu, int E, hipStream_t st);
+// the same maps for a chunk of P (utterance, keyword) pairs, out [P][Tk][Tu][4]: utt bf16 [B][L][Tu][E],
+// utt_mask f32 [B][L][Tu]; pair p = (pair_utt[p], pair_kwd[p]) (device int32 [P]), or with both null the
+// global pair p0 + p = b * K + k.  Indices are clamped into [0, B) / [0, K) in the kernel.
+hipError_t cbw_sim_maps_pairs(const uint16_t* kwd, const float* kwd_mask, int K, const uint16_t* utt,
+                              const float* utt_mask, int B, const int32_t* pair_utt, const int32_t* pair_kwd, int p0,
+                              uint16_t* out, int P, int L, int Tk, int Tu, int E, hipStream_t st);
 // same maps as fp32 NCHW [K][L][Tk][Tu] (KWSOutput.features on request)
 hipError_t cbw_sim_to_nchw(const uint16_t* maps, float* out, int K, int L, int Tk, int Tu, hipStream_t st);
 // ResNet stem conv7x7 s2 p3 over NHWC4 input, BN folded, ReLU. w: bf16 [64][7][8][4] (kw padded to 8)

@@ -241,6 +241,158 @@ __global__ __launch_bounds__(256) void sim_maps_rows_kernel(const bf16* __restri
     }
 }
 
+// ---------------------------------------------------------------- similarity maps of a pair list
+// Pair-indexed variants of the two kernels above (cbw_kws_score_pairs): utt bf16 [B][L][Tu][E] and utt_mask
+// f32 [B][L][Tu] hold B utterances, and pair p of the chunk scores utterance pair_utt[p] against keyword
+// pair_kwd[p]; out [P][Tk][Tu][4] in pair order.  Null index arrays = the full cross product in utterance-major
+// order, global pair p0 + p = b * K + k.  Both indices are clamped into range before any address is formed, so a
+// bad index gives a wrong map, never an out-of-range read.  Per pair the loads, the MFMA order and the epilogue
+// are those of the single-utterance kernels: a pair's map is bit-identical to theirs.
+CBW_DEV void pair_indices(const int32_t* __restrict__ pair_utt, const int32_t* __restrict__ pair_kwd, int p, int p0,
+                          int B, int K, int& b, int& k) {
+    if (pair_utt) {
+        b = pair_utt[p];
+        k = pair_kwd[p];
+    } else {
+        const int g = p0 + p;
+        b = g / K;
+        k = g - b * K;
+    }
+    b = min(max(b, 0), B - 1);
+    k = min(max(k, 0), K - 1);
+}
+
+__global__ __launch_bounds__(256) void sim_maps_pairs_kernel(const bf16* __restrict__ kwd,
+                                                             const float* __restrict__ kwd_mask,
+                                                             const bf16* __restrict__ utt,
+                                                             const float* __restrict__ utt_mask,
+                                                             const int32_t* __restrict__ pair_utt,
+                                                             const int32_t* __restrict__ pair_kwd, int p0,
+                                                             bf16* __restrict__ out, int B, int K, int L, int Tk, int Tu,
+                                                             int E) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int ntu = (Tu + 15) / 16, ntk = (Tk + 15) / 16;
+    const int tu_tile = blockIdx.x * 4 + wv;
+    if (tu_tile >= ntu) return;
+    const int tk_tile = blockIdx.y % ntk;
+    const int p = blockIdx.y / ntk;
+    int b, k;
+    pair_indices(pair_utt, pair_kwd, p, p0, B, K, b, k);
+    utt += (int64_t)b * L * Tu * E;
+    utt_mask += (int64_t)b * L * Tu;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int tk_ld = min(tk_tile * 16 + fr, Tk - 1);
+    const int tu_ld = min(tu_tile * 16 + fr, Tu - 1);
+    f32x4 acc[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) acc[l] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int l = 0; l < L; ++l) {
+        const bf16* ap = kwd + (((int64_t)k * L + l) * Tk + tk_ld) * E + fq * 8;
+        const bf16* bp = utt + ((int64_t)l * Tu + tu_ld) * E + fq * 8;
+        f32x4 c = {0.f, 0.f, 0.f, 0.f};
+        for (int e0 = 0; e0 < E; e0 += 32) {
+            const bf16x8 av = *(const bf16x8*)(ap + e0);
+            const bf16x8 bv = *(const bf16x8*)(bp + e0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, c, 0, 0, 0);
+        }
+        if (l == 0) acc[0] = c; else if (l == 1) acc[1] = c; else if (l == 2) acc[2] = c; else acc[3] = c;
+    }
+    const int tu = tu_tile * 16 + fr;
+    if (tu >= Tu) return;
+    float um[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) um[l] = l < L ? utt_mask[(int64_t)l * Tu + tu] : 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int tk = tk_tile * 16 + fq * 4 + q;
+        if (tk >= Tk) break;
+        bf16x4 o;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const float km = l < L ? kwd_mask[((int64_t)k * L + l) * Tk + tk] : 0.f;
+            o[l] = f2bf(acc[l][q] * um[l] * km);
+        }
+        *(bf16x4*)(out + (((int64_t)p * Tk + tk) * Tu + tu) * 4) = o;
+    }
+}
+
+// Row-strip variant (E = 32 / 64): one block per (16-row tk tile, pair); the block resolves its pair's two
+// indices once and then runs sim_maps_rows_kernel's loop on that keyword and that utterance.
+template <int EC>
+__global__ __launch_bounds__(256) void sim_maps_rows_pairs_kernel(const bf16* __restrict__ kwd,
+                                                                  const float* __restrict__ kwd_mask,
+                                                                  const bf16* __restrict__ utt,
+                                                                  const float* __restrict__ utt_mask,
+                                                                  const int32_t* __restrict__ pair_utt,
+                                                                  const int32_t* __restrict__ pair_kwd, int p0,
+                                                                  bf16* __restrict__ out, int B, int K, int L, int Tk,
+                                                                  int Tu) {
+    constexpr int E = EC * 32;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int ntu = (Tu + 15) / 16;
+    const int tk_tile = blockIdx.x, p = blockIdx.y;
+    int b, k;
+    pair_indices(pair_utt, pair_kwd, p, p0, B, K, b, k);
+    utt += (int64_t)b * L * Tu * E;
+    utt_mask += (int64_t)b * L * Tu;
+    const int tk_ld = min(tk_tile * 16 + fr, Tk - 1);
+    bf16x8 kf[4][EC];
+    float km[4][4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+#pragma unroll
+        for (int ec = 0; ec < EC; ++ec)
+            kf[l][ec] = l < L ? *(const bf16x8*)(kwd + (((int64_t)k * L + l) * Tk + tk_ld) * E + ec * 32 + fq * 8)
+                              : bf16x8{};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int tk = tk_tile * 16 + fq * 4 + q;
+            km[l][q] = (l < L && tk < Tk) ? kwd_mask[((int64_t)k * L + l) * Tk + tk] : 0.f;
+        }
+    }
+    bf16* ok = out + (int64_t)p * Tk * Tu * 4;
+    // the next tile's utterance fragments and mask are loaded while this tile's MFMAs and stores run
+    bf16x8 uf[4][EC];
+    float umn[4];
+    auto load_tile = [&](int t) {
+        const int tu_ld = min(t * 16 + fr, Tu - 1);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+#pragma unroll
+            for (int ec = 0; ec < EC; ++ec)
+                uf[l][ec] = l < L ? *(const bf16x8*)(utt + ((int64_t)l * Tu + tu_ld) * E + ec * 32 + fq * 8) : bf16x8{};
+            umn[l] = l < L ? utt_mask[(int64_t)l * Tu + tu_ld] : 0.f;
+        }
+    };
+    if (wv < ntu) load_tile(wv);
+    for (int t = wv; t < ntu; t += 4) {
+        const int tu = t * 16 + fr;
+        f32x4 c[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            c[l] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ec = 0; ec < EC; ++ec)
+                if (l < L) c[l] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[l][ec], uf[l][ec], c[l], 0, 0, 0);
+        }
+        float um[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) um[l] = umn[l];
+        if (t + 4 < ntu) load_tile(t + 4);
+        if (tu >= Tu) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int tk = tk_tile * 16 + fq * 4 + q;
+            if (tk >= Tk) break;
+            bf16x4 o;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) o[l] = f2bf(c[l][q] * um[l] * km[l][q]);
+            *(bf16x4*)(ok + ((int64_t)tk * Tu + tu) * 4) = o;
+        }
+    }
+}
+
 __global__ void sim_to_nchw_kernel(const bf16* __restrict__ maps, float* __restrict__ out, int K, int L, int Tk, int Tu) {
     const int64_t total = (int64_t)K * Tk * Tu;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1189,6 +1341,29 @@ hipError_t cbw_sim_maps(const uint16_t* kwd, const float* kwd_mask, const uint16
     }
     hipLaunchKernelGGL(sim_maps_kernel, dim3((ntu + 3) / 4, ntk * K), dim3(256), 0, st, (const bf16*)kwd, kwd_mask,
                        (const bf16*)utt, utt_mask, (bf16*)out, K, L, Tk, Tu, E);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sim_maps_pairs(const uint16_t* kwd, const float* kwd_mask, int K, const uint16_t* utt,
+                              const float* utt_mask, int B, const int32_t* pair_utt, const int32_t* pair_kwd, int p0,
+                              uint16_t* out, int P, int L, int Tk, int Tu, int E, hipStream_t st) {
+    if (L > 4 || E % 32 != 0 || B < 1 || K < 1 || p0 < 0 || (pair_utt == nullptr) != (pair_kwd == nullptr))
+        return hipErrorInvalidValue;
+    const int ntu = (Tu + 15) / 16, ntk = (Tk + 15) / 16;
+    if (P <= 0 || Tk <= 0 || Tu <= 0) return hipSuccess;
+    if ((E == 32 || E == 64) && P < 65536) {
+        if (E == 64)
+            hipLaunchKernelGGL(sim_maps_rows_pairs_kernel<2>, dim3(ntk, P), dim3(256), 0, st, (const bf16*)kwd,
+                               kwd_mask, (const bf16*)utt, utt_mask, pair_utt, pair_kwd, p0, (bf16*)out, B, K, L, Tk,
+                               Tu);
+        else
+            hipLaunchKernelGGL(sim_maps_rows_pairs_kernel<1>, dim3(ntk, P), dim3(256), 0, st, (const bf16*)kwd,
+                               kwd_mask, (const bf16*)utt, utt_mask, pair_utt, pair_kwd, p0, (bf16*)out, B, K, L, Tk,
+                               Tu);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(sim_maps_pairs_kernel, dim3((ntu + 3) / 4, ntk * P), dim3(256), 0, st, (const bf16*)kwd,
+                       kwd_mask, (const bf16*)utt, utt_mask, pair_utt, pair_kwd, p0, (bf16*)out, B, K, L, Tk, Tu, E);
     return hipGetLastError();
 }
 

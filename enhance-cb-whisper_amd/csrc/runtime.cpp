@@ -1229,6 +1229,40 @@ int cbw_kws_score(cbw_kws* h, const uint16_t* utt, const float* utt_mask, const 
     return cs.end();
 }
 
+int cbw_kws_score_pairs(cbw_kws* h, const uint16_t* utt, const float* utt_mask, int B, const uint16_t* kwd,
+                        const float* kwd_mask, int K, int Tk, int Tu, const int32_t* pair_utt, const int32_t* pair_kwd,
+                        int P, float* logits, float* features, int chunk, void* ws, int64_t ws_bytes,
+                        cbw_stream_t stream) {
+    if (!h || (P > 0 && (!utt || !utt_mask || !kwd || !kwd_mask || !logits))) return fail(CBW_ERR_INVALID, "null argument");
+    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
+    if (B < 1 || P < 0) return fail(CBW_ERR_INVALID, "bad B/P");
+    if (P == 0) return CBW_OK;
+    if (K < 1 || Tk < 7 || Tu < 7 || chunk <= 0) return fail(CBW_ERR_INVALID, "bad K/Tk/Tu/chunk");
+    if ((pair_utt == nullptr) != (pair_kwd == nullptr))
+        return fail(CBW_ERR_INVALID, "pair_utt and pair_kwd must both be given or both be null");
+    if (!pair_utt && (int64_t)P != (int64_t)B * K)
+        return fail(CBW_ERR_INVALID, "without index arrays P must be B * K (every utterance against every keyword)");
+    if (ws_bytes < cbw_kws_workspace_bytes(h, Tk, Tu, chunk)) return fail(CBW_ERR_OOM, "score workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int L = h->cfg.n_layers;
+    const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
+    const KwsPlan plan = kws_plan(h, Tk, Tu, chunk);
+    const int64_t per = chunk_ws_bytes(h, Tk, Tu, chunk);
+    ChunkStreams cs(h, st, (P + chunk - 1) / chunk);
+    CHK(cs.begin());
+    for (int p0 = 0, i = 0; p0 < P; p0 += chunk, ++i) {
+        const int pc = std::min(chunk, P - p0);
+        hipStream_t s = cs.stream(i);
+        char* w = (char*)ws + cs.slot(i) * per;
+        uint16_t* maps = (uint16_t*)w;
+        HIPCHK(cbw_sim_maps_pairs(kwd, kwd_mask, K, utt, utt_mask, B, pair_utt ? pair_utt + p0 : nullptr,
+                                  pair_kwd ? pair_kwd + p0 : nullptr, p0, maps, pc, L, Tk, Tu, E, s));
+        if (features) HIPCHK(cbw_sim_to_nchw(maps, features + (size_t)p0 * L * Tk * Tu, pc, L, Tk, Tu, s));
+        CHK(resnet_chunk(h, plan, w, pc, Tk, Tu, logits + (size_t)p0 * 2, s));
+    }
+    return cs.end();
+}
+
 int cbw_kws_score_fp8(cbw_kws* h, const uint16_t* utt, const float* utt_mask, const uint16_t* kwd,
                       const float* kwd_mask, int K, int Tk, int Tu, float* logits, int chunk, void* ws, int64_t ws_bytes,
                       cbw_stream_t stream) {

@@ -193,9 +193,9 @@ class KWSModel:
                         logits = eng.score(pu[0], pum[0], pk, pkm)   # the bias-corrected bf16 network
                 logits = self._rescore_band(eng, kwd, km, utt, um, pkm, pum, logits)
         else:  # training-style batches: one utterance per keyword
-            res = [eng.score(pu[i], pum[i], pk[i:i + 1], pkm[i:i + 1], features=return_features) for i in range(K)]
-            logits = torch.cat([r[0] if return_features else r for r in res], 0)
-            feats = torch.cat([r[1] for r in res], 0) if return_features else None
+            pair = torch.arange(K, dtype=torch.int32, device=dev)
+            out = eng.score_pairs(pu, pum, pk, pkm, pair, pair, features=return_features, trusted=True)
+            logits, feats = out if return_features else (out, None)
         loss = None
         if labels is not None:
             loss = torch.nn.functional.cross_entropy(logits, labels.to(dev).view(-1))

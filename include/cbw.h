@@ -80,6 +80,17 @@ int cbw_kws_score(cbw_kws* h, const uint16_t* utt, const float* utt_mask, const 
                   int K, int Tk, int Tu, float* logits, float* features, int chunk, void* ws, int64_t ws_bytes,
                   cbw_stream_t stream);
 
+/* forward tail for a list of (utterance, keyword) pairs (model.py:171-193 with utt batch == n_keywords, and
+ * batches of utterances against one keyword set): utt bf16 [B][L][Tu][E], utt_mask f32 [B][L][Tu], kwd / kwd_mask
+ * as cbw_kws_score; pair p scores utterance pair_utt[p] against keyword pair_kwd[p] (device int32 [P], clamped
+ * into range on the device); both NULL = every utterance against every keyword, p = b * K + k, and P must be B * K.
+ * logits f32 [P][2] in pair order; features (optional) f32 [P][L][Tk][Tu].  Chunks of `chunk` pairs may span
+ * utterances.  P == 0 returns CBW_OK and writes nothing.  Workspace: cbw_kws_workspace_bytes. */
+int cbw_kws_score_pairs(cbw_kws* h, const uint16_t* utt, const float* utt_mask, int B, const uint16_t* kwd,
+                        const float* kwd_mask, int K, int Tk, int Tu, const int32_t* pair_utt, const int32_t* pair_kwd,
+                        int P, float* logits, float* features, int chunk, void* ws, int64_t ws_bytes,
+                        cbw_stream_t stream);
+
 /* fp8 first tier of the exact-decision cascade (BASELINE C5 "fp8 MFMA"; the ResNet of efficient_kws/resnet.py:51-58
  * called at efficient_kws/model.py:193): the stem and stage 1 on the bf16 network, stages 2-4 of ResNet-50 on
  * e4m3 operands (v_mfma_scale_f32_16x16x128_f8f6f4), one static scale per activation tensor, per-channel weight
