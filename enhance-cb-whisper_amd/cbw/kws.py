@@ -272,26 +272,11 @@ class KwsEngine:
     def score_fp8(self, utt: torch.Tensor, utt_mask: torch.Tensor, kwd: torch.Tensor, kwd_mask: torch.Tensor,
                   chunk: Optional[int] = None, logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Logits of every pair from the fp8 tier (cbw_kws_score_fp8); inputs as ``score``."""
-        if utt.dim() == 4:
-            utt, utt_mask = utt[0], utt_mask.reshape(utt_mask.shape[-2:])
-        K, L, Tk, E = kwd.shape
+        utt, utt_mask, kwd, kwd_mask = self._check_single(utt, utt_mask, kwd, kwd_mask)
+        K, _, Tk, _ = kwd.shape
         Tu = utt.shape[1]
-        if L != self.n_layers or E != self.feat_dim or tuple(utt.shape) != (L, Tu, E):
-            raise ValueError(f"shape mismatch: kwd {tuple(kwd.shape)} utt {tuple(utt.shape)}")
-        if utt.dtype != torch.bfloat16 or kwd.dtype != torch.bfloat16:
-            raise ValueError("projected features must be bf16 (use KwsEngine.project)")
-        if utt_mask.numel() == L * Tu:
-            utt_mask = utt_mask.reshape(L, Tu)
-        if tuple(kwd_mask.shape) != (K, L, Tk) or tuple(utt_mask.shape) != (L, Tu):
-            raise ValueError("mask shapes")
         chunk = chunk or self.default_chunk(Tk, Tu)
-        if logits_out is not None and (tuple(logits_out.shape) != (K, 2) or logits_out.dtype != torch.float32
-                                       or not logits_out.is_contiguous()):
-            raise ValueError(f"logits_out must be contiguous f32 [{K}, 2]")
-        logits = logits_out if logits_out is not None else torch.empty((K, 2), dtype=torch.float32, device=self.device)
-        utt, kwd = utt.contiguous(), kwd.contiguous()
-        utt_mask = utt_mask.to(torch.float32).contiguous()
-        kwd_mask = kwd_mask.to(torch.float32).contiguous()
+        logits = self._logits(logits_out, (K, 2))
         with torch.cuda.device(self.device):
             ws = self.workspace(Tk, Tu, chunk)
             _lib.check(self.lib.cbw_kws_score_fp8(self.h, utt.data_ptr(), utt_mask.data_ptr(), kwd.data_ptr(),
@@ -390,22 +375,11 @@ class KwsEngine:
               features: bool = False, chunk: Optional[int] = None, logits_out: Optional[torch.Tensor] = None):
         """utt bf16 [L, Tu, E] (or [1, L, Tu, E]), utt_mask f32 [L, Tu]; kwd bf16 [K, L, Tk, E],
         kwd_mask f32 [K, L, Tk]  ->  logits f32 [K, 2] (+ features f32 [K, L, Tk, Tu])."""
-        if utt.dim() == 4:
-            utt, utt_mask = utt[0], utt_mask.reshape(utt_mask.shape[-2:])
-        K, L, Tk, E = kwd.shape
+        utt, utt_mask, kwd, kwd_mask = self._check_single(utt, utt_mask, kwd, kwd_mask)
+        K, L, Tk, _ = kwd.shape
         Tu = utt.shape[1]
-        if L != self.n_layers or E != self.feat_dim or tuple(utt.shape) != (L, Tu, E):
-            raise ValueError(f"shape mismatch: kwd {tuple(kwd.shape)} utt {tuple(utt.shape)}")
-        if utt.dtype != torch.bfloat16 or kwd.dtype != torch.bfloat16:
-            raise ValueError("projected features must be bf16 (use KwsEngine.project)")
-        utt, kwd = utt.contiguous(), kwd.contiguous()
-        utt_mask = utt_mask.to(torch.float32).contiguous()
-        kwd_mask = kwd_mask.to(torch.float32).contiguous()
         chunk = chunk or self.default_chunk(Tk, Tu)
-        if logits_out is not None and (tuple(logits_out.shape) != (K, 2) or logits_out.dtype != torch.float32
-                                       or not logits_out.is_contiguous()):
-            raise ValueError(f"logits_out must be contiguous f32 [{K}, 2], got {tuple(logits_out.shape)}")
-        logits = logits_out if logits_out is not None else torch.empty((K, 2), dtype=torch.float32, device=self.device)
+        logits = self._logits(logits_out, (K, 2))
         feats = torch.empty((K, L, Tk, Tu), dtype=torch.float32, device=self.device) if features else None
         with torch.cuda.device(self.device):
             ws = self.workspace(Tk, Tu, chunk)
@@ -413,6 +387,35 @@ class KwsEngine:
                                               kwd_mask.data_ptr(), K, Tk, Tu, logits.data_ptr(), _lib.ptr(feats), chunk,
                                               ws.data_ptr(), ws.numel(), _lib.stream_handle()), "cbw_kws_score")
         return (logits, feats) if features else logits
+
+    def _check_single(self, utt, utt_mask, kwd, kwd_mask):
+        """Shape / dtype checks of ``score`` and ``score_fp8``: utt bf16 [L, Tu, E] or [1, L, Tu, E], a utt_mask of
+        L * Tu elements (reshaped to [L, Tu]), kwd bf16 [K, L, Tk, E], kwd_mask [K, L, Tk].  Returns the four
+        tensors contiguous, the masks in f32."""
+        if utt.dim() == 4:
+            utt = utt[0]
+        if utt.dim() != 3 or kwd.dim() != 4:
+            raise ValueError(f"expected utt [L, Tu, E] and kwd [K, L, Tk, E], got {tuple(utt.shape)} "
+                             f"{tuple(kwd.shape)}")
+        K, L, Tk, E = kwd.shape
+        Tu = utt.shape[1]
+        if L != self.n_layers or E != self.feat_dim or tuple(utt.shape) != (L, Tu, E):
+            raise ValueError(f"shape mismatch: kwd {tuple(kwd.shape)} utt {tuple(utt.shape)}")
+        if utt.dtype != torch.bfloat16 or kwd.dtype != torch.bfloat16:
+            raise ValueError("projected features must be bf16 (use KwsEngine.project)")
+        if tuple(kwd_mask.shape) != (K, L, Tk) or utt_mask.numel() != L * Tu:
+            raise ValueError(f"mask shapes {tuple(kwd_mask.shape)} {tuple(utt_mask.shape)} for kwd {tuple(kwd.shape)} "
+                             f"utt {tuple(utt.shape)}")
+        return (utt.contiguous(), utt_mask.reshape(L, Tu).to(torch.float32).contiguous(), kwd.contiguous(),
+                kwd_mask.to(torch.float32).contiguous())
+
+    def _logits(self, logits_out, shape):
+        """The caller's ``logits_out`` if it is a contiguous f32 tensor of ``shape``, a new tensor if None."""
+        if logits_out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(logits_out.shape) != shape or logits_out.dtype != torch.float32 or not logits_out.is_contiguous():
+            raise ValueError(f"logits_out must be contiguous f32 {list(shape)}, got {tuple(logits_out.shape)}")
+        return logits_out
 
     def _check_batch(self, utt, utt_mask, kwd, kwd_mask):
         """Shape / dtype checks of ``score`` for a batch of utterances: utt bf16 [B, L, Tu, E]."""
@@ -459,20 +462,24 @@ class KwsEngine:
             raise ValueError(f"pair_utt has {P} entries, pair_kwd {pk.numel()}")
         if P > 0 and K < 1:
             raise ValueError("pairs given but no keywords")
-        if logits_out is not None and (tuple(logits_out.shape) != (P, 2) or logits_out.dtype != torch.float32
-                                       or not logits_out.is_contiguous()):
-            raise ValueError(f"logits_out must be contiguous f32 [{P}, 2], got {tuple(logits_out.shape)}")
-        logits = logits_out if logits_out is not None else torch.empty((P, 2), dtype=torch.float32, device=self.device)
+        logits = self._logits(logits_out, (P, 2))
         feats = torch.empty((P, L, Tk, Tu), dtype=torch.float32, device=self.device) if features else None
-        if P > 0:
-            chunk = chunk or self.default_chunk(Tk, Tu)
-            with torch.cuda.device(self.device):
-                ws = self.workspace(Tk, Tu, chunk)
-                _lib.check(self.lib.cbw_kws_score_pairs(
-                    self.h, utt.data_ptr(), utt_mask.data_ptr(), B, kwd.data_ptr(), kwd_mask.data_ptr(), K, Tk, Tu,
-                    pu.data_ptr(), pk.data_ptr(), P, logits.data_ptr(), _lib.ptr(feats), chunk, ws.data_ptr(),
-                    ws.numel(), _lib.stream_handle()), "cbw_kws_score_pairs")
+        self._call_score_pairs(utt, utt_mask, kwd, kwd_mask, pu, pk, P, logits, feats, chunk)
         return (logits, feats) if features else logits
+
+    def _call_score_pairs(self, utt, utt_mask, kwd, kwd_mask, pu, pk, P, logits, feats, chunk):
+        """cbw_kws_score_pairs on checked inputs (``_check_batch``); pu / pk None = every utterance x every keyword."""
+        if P == 0:
+            return
+        K, _, Tk, _ = kwd.shape
+        B, _, Tu, _ = utt.shape
+        chunk = chunk or self.default_chunk(Tk, Tu)
+        with torch.cuda.device(self.device):
+            ws = self.workspace(Tk, Tu, chunk)
+            _lib.check(self.lib.cbw_kws_score_pairs(
+                self.h, utt.data_ptr(), utt_mask.data_ptr(), B, kwd.data_ptr(), kwd_mask.data_ptr(), K, Tk, Tu,
+                _lib.ptr(pu), _lib.ptr(pk), P, logits.data_ptr(), _lib.ptr(feats), chunk, ws.data_ptr(), ws.numel(),
+                _lib.stream_handle()), "cbw_kws_score_pairs")
 
     def score_batch(self, utt: torch.Tensor, utt_mask: torch.Tensor, kwd: torch.Tensor, kwd_mask: torch.Tensor,
                     chunk: Optional[int] = None, logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -480,21 +487,9 @@ class KwsEngine:
         chunks of pairs may span utterances): utt bf16 [B, L, Tu, E], utt_mask f32 [B, L, Tu]  ->  logits f32
         [B, K, 2], row b what ``score`` gives for utterance b."""
         utt, utt_mask, kwd, kwd_mask = self._check_batch(utt, utt_mask, kwd, kwd_mask)
-        K, L, Tk, _ = kwd.shape
-        B, _, Tu, _ = utt.shape
-        if logits_out is not None and (tuple(logits_out.shape) != (B, K, 2) or logits_out.dtype != torch.float32
-                                       or not logits_out.is_contiguous()):
-            raise ValueError(f"logits_out must be contiguous f32 [{B}, {K}, 2], got {tuple(logits_out.shape)}")
-        logits = (logits_out if logits_out is not None
-                  else torch.empty((B, K, 2), dtype=torch.float32, device=self.device))
-        if K > 0:
-            chunk = chunk or self.default_chunk(Tk, Tu)
-            with torch.cuda.device(self.device):
-                ws = self.workspace(Tk, Tu, chunk)
-                _lib.check(self.lib.cbw_kws_score_pairs(
-                    self.h, utt.data_ptr(), utt_mask.data_ptr(), B, kwd.data_ptr(), kwd_mask.data_ptr(), K, Tk, Tu,
-                    None, None, B * K, logits.data_ptr(), None, chunk, ws.data_ptr(), ws.numel(),
-                    _lib.stream_handle()), "cbw_kws_score_pairs")
+        B, K = utt.shape[0], kwd.shape[0]
+        logits = self._logits(logits_out, (B, K, 2))
+        self._call_score_pairs(utt, utt_mask, kwd, kwd_mask, None, None, B * K, logits, None, chunk)
         return logits
 
     def classify(self, maps: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:

@@ -122,16 +122,17 @@ __global__ __launch_bounds__(64) void lef_time_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------- similarity maps
-// one wave per 16x16 (tk, tu) tile, all L layers; block = 4 waves along tu.
-__global__ __launch_bounds__(256) void sim_maps_kernel(const bf16* __restrict__ kwd, const float* __restrict__ kwd_mask,
-                                                       const bf16* __restrict__ utt, const float* __restrict__ utt_mask,
-                                                       bf16* __restrict__ out, int K, int L, int Tk, int Tu, int E) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int ntu = (Tu + 15) / 16, ntk = (Tk + 15) / 16;
-    const int tu_tile = blockIdx.x * 4 + wv;
-    if (tu_tile >= ntu) return;
-    const int tk_tile = blockIdx.y % ntk;
-    const int k = blockIdx.y / ntk;
+// The two device bodies below compute one (keyword, utterance) map from its five base pointers: kwd bf16
+// [L][Tk][E] and kwd_mask f32 [L][Tk] of the keyword, utt bf16 [L][Tu][E] and utt_mask f32 [L][Tu] of the
+// utterance, out bf16 [Tk][Tu][4].  The __global__ kernels only resolve which keyword (and, for a pair list,
+// which utterance) a block works on, offset the pointers and call a body, so the single-utterance and the
+// pair-indexed kernels share their loads, MFMA order and epilogue: a pair's map is bit-identical by construction.
+//
+// sim_tile_body: one wave computes the 16x16 tile (tk_tile, tu_tile) of all L layers, any E % 32 == 0.
+CBW_DEV void sim_tile_body(const bf16* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                           const bf16* __restrict__ utt, const float* __restrict__ utt_mask, bf16* __restrict__ out,
+                           int tk_tile, int tu_tile, int L, int Tk, int Tu, int E) {
+    const int lane = threadIdx.x & 63;
     const int fr = lane & 15, fq = lane >> 4;
     const int tk_ld = min(tk_tile * 16 + fr, Tk - 1);
     const int tu_ld = min(tu_tile * 16 + fr, Tu - 1);
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void sim_maps_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int l = 0; l < 4; ++l) acc[l] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int l = 0; l < L; ++l) {
-        const bf16* ap = kwd + (((int64_t)k * L + l) * Tk + tk_ld) * E + fq * 8;
+        const bf16* ap = kwd + ((int64_t)l * Tk + tk_ld) * E + fq * 8;
         const bf16* bp = utt + ((int64_t)l * Tu + tu_ld) * E + fq * 8;
         f32x4 c = {0.f, 0.f, 0.f, 0.f};
         for (int e0 = 0; e0 < E; e0 += 32) {
@@ -161,29 +162,26 @@ __global__ __launch_bounds__(256) void sim_maps_kernel(const bf16* __restrict__ 
         bf16x4 o;
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            const float km = l < L ? kwd_mask[((int64_t)k * L + l) * Tk + tk] : 0.f;
+            const float km = l < L ? kwd_mask[(int64_t)l * Tk + tk] : 0.f;
             o[l] = f2bf(acc[l][q] * um[l] * km);
         }
-        *(bf16x4*)(out + (((int64_t)k * Tk + tk) * Tu + tu) * 4) = o;
+        *(bf16x4*)(out + ((int64_t)tk * Tu + tu) * 4) = o;
     }
 }
 
-// Row-strip variant for E <= 64 (LE / LEF projected features): one block per (keyword, 16-row tk tile),
-// its 4 waves walk the tu tiles 4 apart.  The keyword fragments and masks are loaded once per wave and
+// sim_rows_body, for E <= 64 (LE / LEF projected features): the block's 4 waves walk the tu tiles of one
+// 16-row tk tile 4 apart.  The keyword fragments and masks are loaded once per wave and
 // the utterance fragments (shared by every keyword: L2-resident) once per tile, so a wave streams
 // 16 x 16 x 4-channel output tiles back to back instead of paying a launch and a load chain per tile
-// (LEF chunk of 500 pairs: 182 us for the one-tile-per-wave kernel above, which stays for large E).
+// (LEF chunk of 500 pairs: 182 us for the one-tile-per-wave body above, which stays for large E).
 template <int EC>
-__global__ __launch_bounds__(256) void sim_maps_rows_kernel(const bf16* __restrict__ kwd,
-                                                            const float* __restrict__ kwd_mask,
-                                                            const bf16* __restrict__ utt,
-                                                            const float* __restrict__ utt_mask,
-                                                            bf16* __restrict__ out, int L, int Tk, int Tu) {
+CBW_DEV void sim_rows_body(const bf16* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                           const bf16* __restrict__ utt, const float* __restrict__ utt_mask, bf16* __restrict__ out,
+                           int tk_tile, int L, int Tk, int Tu) {
     constexpr int E = EC * 32;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int fr = lane & 15, fq = lane >> 4;
     const int ntu = (Tu + 15) / 16;
-    const int tk_tile = blockIdx.x, k = blockIdx.y;
     const int tk_ld = min(tk_tile * 16 + fr, Tk - 1);
     bf16x8 kf[4][EC];
     float km[4][4];
@@ -191,15 +189,13 @@ __global__ __launch_bounds__(256) void sim_maps_rows_kernel(const bf16* __restri
     for (int l = 0; l < 4; ++l) {
 #pragma unroll
         for (int ec = 0; ec < EC; ++ec)
-            kf[l][ec] = l < L ? *(const bf16x8*)(kwd + (((int64_t)k * L + l) * Tk + tk_ld) * E + ec * 32 + fq * 8)
-                              : bf16x8{};
+            kf[l][ec] = l < L ? *(const bf16x8*)(kwd + ((int64_t)l * Tk + tk_ld) * E + ec * 32 + fq * 8) : bf16x8{};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int tk = tk_tile * 16 + fq * 4 + q;
-            km[l][q] = (l < L && tk < Tk) ? kwd_mask[((int64_t)k * L + l) * Tk + tk] : 0.f;
+            km[l][q] = (l < L && tk < Tk) ? kwd_mask[(int64_t)l * Tk + tk] : 0.f;
         }
     }
-    bf16* ok = out + (int64_t)k * Tk * Tu * 4;
     // the next tile's utterance fragments and mask are loaded while this tile's MFMAs and stores run
     bf16x8 uf[4][EC];
     float umn[4];
@@ -236,18 +232,42 @@ __global__ __launch_bounds__(256) void sim_maps_rows_kernel(const bf16* __restri
             bf16x4 o;
 #pragma unroll
             for (int l = 0; l < 4; ++l) o[l] = f2bf(c[l][q] * um[l] * km[l][q]);
-            *(bf16x4*)(ok + ((int64_t)tk * Tu + tu) * 4) = o;
+            *(bf16x4*)(out + ((int64_t)tk * Tu + tu) * 4) = o;
         }
     }
 }
 
-// ---------------------------------------------------------------- similarity maps of a pair list
-// Pair-indexed variants of the two kernels above (cbw_kws_score_pairs): utt bf16 [B][L][Tu][E] and utt_mask
-// f32 [B][L][Tu] hold B utterances, and pair p of the chunk scores utterance pair_utt[p] against keyword
-// pair_kwd[p]; out [P][Tk][Tu][4] in pair order.  Null index arrays = the full cross product in utterance-major
-// order, global pair p0 + p = b * K + k.  Both indices are clamped into range before any address is formed, so a
-// bad index gives a wrong map, never an out-of-range read.  Per pair the loads, the MFMA order and the epilogue
-// are those of the single-utterance kernels: a pair's map is bit-identical to theirs.
+// One utterance against K keywords (cbw_sim_maps): kwd [K][L][Tk][E], out [K][Tk][Tu][4].
+// sim_maps_kernel: block = 4 waves along tu, grid.y = (keyword, tk tile).
+__global__ __launch_bounds__(256) void sim_maps_kernel(const bf16* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                                                       const bf16* __restrict__ utt, const float* __restrict__ utt_mask,
+                                                       bf16* __restrict__ out, int K, int L, int Tk, int Tu, int E) {
+    const int ntu = (Tu + 15) / 16, ntk = (Tk + 15) / 16;
+    const int tu_tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tu_tile >= ntu) return;
+    const int tk_tile = blockIdx.y % ntk;
+    const int k = blockIdx.y / ntk;
+    sim_tile_body(kwd + (int64_t)k * L * Tk * E, kwd_mask + (int64_t)k * L * Tk, utt, utt_mask,
+                  out + (int64_t)k * Tk * Tu * 4, tk_tile, tu_tile, L, Tk, Tu, E);
+}
+
+// sim_maps_rows_kernel: one block per (16-row tk tile, keyword).
+template <int EC>
+__global__ __launch_bounds__(256) void sim_maps_rows_kernel(const bf16* __restrict__ kwd,
+                                                            const float* __restrict__ kwd_mask,
+                                                            const bf16* __restrict__ utt,
+                                                            const float* __restrict__ utt_mask,
+                                                            bf16* __restrict__ out, int L, int Tk, int Tu) {
+    const int k = blockIdx.y;
+    sim_rows_body<EC>(kwd + (int64_t)k * L * Tk * EC * 32, kwd_mask + (int64_t)k * L * Tk, utt, utt_mask,
+                      out + (int64_t)k * Tk * Tu * 4, blockIdx.x, L, Tk, Tu);
+}
+
+// A pair list (cbw_sim_maps_pairs): utt bf16 [B][L][Tu][E] and utt_mask f32 [B][L][Tu] hold B utterances, and
+// pair p of the chunk scores utterance pair_utt[p] against keyword pair_kwd[p]; out [P][Tk][Tu][4] in pair order.
+// Null index arrays = the full cross product in utterance-major order, global pair p0 + p = b * K + k.  Both
+// indices are clamped into range before any address is formed, so a bad index gives a wrong map, never an
+// out-of-range read.  Same grids as the two kernels above with the pair in the keyword's place.
 CBW_DEV void pair_indices(const int32_t* __restrict__ pair_utt, const int32_t* __restrict__ pair_kwd, int p, int p0,
                           int B, int K, int& b, int& k) {
     if (pair_utt) {
@@ -270,54 +290,17 @@ __global__ __launch_bounds__(256) void sim_maps_pairs_kernel(const bf16* __restr
                                                              const int32_t* __restrict__ pair_kwd, int p0,
                                                              bf16* __restrict__ out, int B, int K, int L, int Tk, int Tu,
                                                              int E) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ntu = (Tu + 15) / 16, ntk = (Tk + 15) / 16;
-    const int tu_tile = blockIdx.x * 4 + wv;
+    const int tu_tile = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tu_tile >= ntu) return;
     const int tk_tile = blockIdx.y % ntk;
     const int p = blockIdx.y / ntk;
     int b, k;
     pair_indices(pair_utt, pair_kwd, p, p0, B, K, b, k);
-    utt += (int64_t)b * L * Tu * E;
-    utt_mask += (int64_t)b * L * Tu;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int tk_ld = min(tk_tile * 16 + fr, Tk - 1);
-    const int tu_ld = min(tu_tile * 16 + fr, Tu - 1);
-    f32x4 acc[4];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) acc[l] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int l = 0; l < L; ++l) {
-        const bf16* ap = kwd + (((int64_t)k * L + l) * Tk + tk_ld) * E + fq * 8;
-        const bf16* bp = utt + ((int64_t)l * Tu + tu_ld) * E + fq * 8;
-        f32x4 c = {0.f, 0.f, 0.f, 0.f};
-        for (int e0 = 0; e0 < E; e0 += 32) {
-            const bf16x8 av = *(const bf16x8*)(ap + e0);
-            const bf16x8 bv = *(const bf16x8*)(bp + e0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, c, 0, 0, 0);
-        }
-        if (l == 0) acc[0] = c; else if (l == 1) acc[1] = c; else if (l == 2) acc[2] = c; else acc[3] = c;
-    }
-    const int tu = tu_tile * 16 + fr;
-    if (tu >= Tu) return;
-    float um[4];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) um[l] = l < L ? utt_mask[(int64_t)l * Tu + tu] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int tk = tk_tile * 16 + fq * 4 + q;
-        if (tk >= Tk) break;
-        bf16x4 o;
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            const float km = l < L ? kwd_mask[((int64_t)k * L + l) * Tk + tk] : 0.f;
-            o[l] = f2bf(acc[l][q] * um[l] * km);
-        }
-        *(bf16x4*)(out + (((int64_t)p * Tk + tk) * Tu + tu) * 4) = o;
-    }
+    sim_tile_body(kwd + (int64_t)k * L * Tk * E, kwd_mask + (int64_t)k * L * Tk, utt + (int64_t)b * L * Tu * E,
+                  utt_mask + (int64_t)b * L * Tu, out + (int64_t)p * Tk * Tu * 4, tk_tile, tu_tile, L, Tk, Tu, E);
 }
 
-// Row-strip variant (E = 32 / 64): one block per (16-row tk tile, pair); the block resolves its pair's two
-// indices once and then runs sim_maps_rows_kernel's loop on that keyword and that utterance.
 template <int EC>
 __global__ __launch_bounds__(256) void sim_maps_rows_pairs_kernel(const bf16* __restrict__ kwd,
                                                                   const float* __restrict__ kwd_mask,
@@ -328,69 +311,11 @@ __global__ __launch_bounds__(256) void sim_maps_rows_pairs_kernel(const bf16* __
                                                                   bf16* __restrict__ out, int B, int K, int L, int Tk,
                                                                   int Tu) {
     constexpr int E = EC * 32;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int ntu = (Tu + 15) / 16;
-    const int tk_tile = blockIdx.x, p = blockIdx.y;
+    const int p = blockIdx.y;
     int b, k;
     pair_indices(pair_utt, pair_kwd, p, p0, B, K, b, k);
-    utt += (int64_t)b * L * Tu * E;
-    utt_mask += (int64_t)b * L * Tu;
-    const int tk_ld = min(tk_tile * 16 + fr, Tk - 1);
-    bf16x8 kf[4][EC];
-    float km[4][4];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-#pragma unroll
-        for (int ec = 0; ec < EC; ++ec)
-            kf[l][ec] = l < L ? *(const bf16x8*)(kwd + (((int64_t)k * L + l) * Tk + tk_ld) * E + ec * 32 + fq * 8)
-                              : bf16x8{};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int tk = tk_tile * 16 + fq * 4 + q;
-            km[l][q] = (l < L && tk < Tk) ? kwd_mask[((int64_t)k * L + l) * Tk + tk] : 0.f;
-        }
-    }
-    bf16* ok = out + (int64_t)p * Tk * Tu * 4;
-    // the next tile's utterance fragments and mask are loaded while this tile's MFMAs and stores run
-    bf16x8 uf[4][EC];
-    float umn[4];
-    auto load_tile = [&](int t) {
-        const int tu_ld = min(t * 16 + fr, Tu - 1);
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-#pragma unroll
-            for (int ec = 0; ec < EC; ++ec)
-                uf[l][ec] = l < L ? *(const bf16x8*)(utt + ((int64_t)l * Tu + tu_ld) * E + ec * 32 + fq * 8) : bf16x8{};
-            umn[l] = l < L ? utt_mask[(int64_t)l * Tu + tu_ld] : 0.f;
-        }
-    };
-    if (wv < ntu) load_tile(wv);
-    for (int t = wv; t < ntu; t += 4) {
-        const int tu = t * 16 + fr;
-        f32x4 c[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            c[l] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ec = 0; ec < EC; ++ec)
-                if (l < L) c[l] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[l][ec], uf[l][ec], c[l], 0, 0, 0);
-        }
-        float um[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) um[l] = umn[l];
-        if (t + 4 < ntu) load_tile(t + 4);
-        if (tu >= Tu) continue;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int tk = tk_tile * 16 + fq * 4 + q;
-            if (tk >= Tk) break;
-            bf16x4 o;
-#pragma unroll
-            for (int l = 0; l < 4; ++l) o[l] = f2bf(c[l][q] * um[l] * km[l][q]);
-            *(bf16x4*)(ok + ((int64_t)tk * Tu + tu) * 4) = o;
-        }
-    }
+    sim_rows_body<EC>(kwd + (int64_t)k * L * Tk * E, kwd_mask + (int64_t)k * L * Tk, utt + (int64_t)b * L * Tu * E,
+                      utt_mask + (int64_t)b * L * Tu, out + (int64_t)p * Tk * Tu * 4, blockIdx.x, L, Tk, Tu);
 }
 
 __global__ void sim_to_nchw_kernel(const bf16* __restrict__ maps, float* __restrict__ out, int K, int L, int Tk, int Tu) {

@@ -183,6 +183,33 @@ struct Prof {
     int cur_tier = 0;
     int used = 0;
     ~Prof() { for (auto e : ev) (void)hipEventDestroy(e); }
+    // One record brackets one launch on stream st.  begin() records the first event and gives the record's slot
+    // (-1: no profile, profiling off or the table full); end() is called only after the launch succeeded, so an error
+    // return between the two leaves `used` unchanged.  p may be null.
+    static int begin(Prof* p, hipStream_t st, int* slot) {
+        *slot = (p && p->on && (size_t)(2 * p->used + 1) < p->ev.size()) ? p->used : -1;
+        if (*slot >= 0) HIPCHK(hipEventRecord(p->ev[2 * *slot], st));
+        return CBW_OK;
+    }
+    static int end(Prof* p, int slot, hipStream_t st, double flops, const char* kernel, int tier_ = -1) {
+        if (slot < 0) return CBW_OK;
+        HIPCHK(hipEventRecord(p->ev[2 * slot + 1], st));
+        p->flop[slot] = flops;
+        p->tier[slot] = tier_ < 0 ? p->cur_tier : tier_;
+        p->kern[slot] = kernel;
+        p->used++;
+        return CBW_OK;
+    }
+};
+
+// cur_tier for the records of one scoring call, put back on every path out of the scope
+struct TierScope {
+    Prof& p;
+    const int saved;
+    TierScope(Prof& p_, int tier) : p(p_), saved(p_.cur_tier) { p.cur_tier = tier; }
+    ~TierScope() { p.cur_tier = saved; }
+    TierScope(const TierScope&) = delete;
+    TierScope& operator=(const TierScope&) = delete;
 };
 
 struct Src2 {   // second K-source of a fused 1x1 conv (ConvArgs::x2)
@@ -205,19 +232,13 @@ int launch_conv(const ConvW& c, const void* x, int N, int H, int W, void* y, con
     a.flags = flags | (c.relu ? CBW_EPI_RELU : 0);
     if (Ho_out) *Ho_out = a.Ho;
     if (Wo_out) *Wo_out = a.Wo;
-    const bool rec = prof && prof->on && (size_t)(2 * prof->used + 1) < prof->ev.size();
-    if (rec) HIPCHK(hipEventRecord(prof->ev[2 * prof->used], st));
+    int slot;
+    CHK(Prof::begin(prof, st, &slot));
     cbw_last_conv_kernel = "?";
     if (splitk_ws) HIPCHK(cbw_conv_igemm_splitk(a, cbw_conv_splitk_factor(a), splitk_ws, st));
     else HIPCHK(cbw_conv_igemm(a, st));
-    if (rec) {
-        HIPCHK(hipEventRecord(prof->ev[2 * prof->used + 1], st));
-        prof->flop[prof->used] = 2.0 * a.M * a.Cout * ((double)a.Cin * a.KH * a.KW + (a.x2 ? a.Cin2 : 0));
-        prof->tier[prof->used] = prof->cur_tier;
-        prof->kern[prof->used] = cbw_last_conv_kernel;
-        prof->used++;
-    }
-    return CBW_OK;
+    return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * ((double)a.Cin * a.KH * a.KW + (a.x2 ? a.Cin2 : 0)),
+                     cbw_last_conv_kernel);
 }
 
 // Block b's identity expand (c2: t2 -> y with residual res and ReLU) and block b + 1's 1x1 reduce (r0: y -> t1n) as
@@ -240,17 +261,12 @@ int launch_chain(const ConvW& c2, const ConvW& r0, const DevBuf& r0_packed, cons
     r.x = y; r.w = r0.w.p; r.bias = r0.b.as<float>(); r.res = nullptr; r.y = t1n;
     r.Cin = r0.cin; r.Cout = r0.cout; r.res_ld = r.y_ld = r0.cout;
     if (!cbw_conv_stream_wanted(a) || !cbw_conv_stream_wanted(r) || !cbw_conv_chain_supported(a, r0.cout)) return CBW_OK;
-    const bool rec = prof && prof->on && (size_t)(2 * prof->used + 1) < prof->ev.size();
-    if (rec) HIPCHK(hipEventRecord(prof->ev[2 * prof->used], st));
+    int slot;
+    CHK(Prof::begin(prof, st, &slot));
     cbw_last_conv_kernel = "?";
     HIPCHK(cbw_conv_chain(a, r0_packed.as<uint16_t>(), r0.b.as<float>(), t1n, st));
-    if (rec) {
-        HIPCHK(hipEventRecord(prof->ev[2 * prof->used + 1], st));
-        prof->flop[prof->used] = 2.0 * a.M * a.Cout * (double)a.Cin + 2.0 * a.M * r0.cout * (double)r0.cin;
-        prof->tier[prof->used] = prof->cur_tier;
-        prof->kern[prof->used] = cbw_last_conv_kernel;
-        prof->used++;
-    }
+    CHK(Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin + 2.0 * a.M * r0.cout * (double)r0.cin,
+                  cbw_last_conv_kernel));
     *done = true;
     return CBW_OK;
 }
@@ -358,18 +374,12 @@ int launch_conv_x3(const ConvW& c, const void* x, int N, int H, int W, void* y, 
     a.flags = flags | (res ? (res_split ? CBW_EPI_RES_SPLIT : CBW_EPI_RES_F32) : 0) | (c.relu ? CBW_EPI_RELU : 0);
     if (Ho_out) *Ho_out = a.Ho;
     if (Wo_out) *Wo_out = a.Wo;
-    const bool rec = prof && prof->on && (size_t)(2 * prof->used + 1) < prof->ev.size();
-    if (rec) HIPCHK(hipEventRecord(prof->ev[2 * prof->used], st));
+    int slot;
+    CHK(Prof::begin(prof, st, &slot));
     cbw_last_conv_kernel = "?";
     HIPCHK(cbw_conv_igemm(a, st));
-    if (rec) {   // the compensated conv's GEMM: K over the three split segments
-        HIPCHK(hipEventRecord(prof->ev[2 * prof->used + 1], st));
-        prof->flop[prof->used] = 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW;
-        prof->tier[prof->used] = 1;
-        prof->kern[prof->used] = cbw_last_conv_kernel;
-        prof->used++;
-    }
-    return CBW_OK;
+    // the compensated conv's GEMM: K over the three split segments; always tier 1
+    return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel, 1);
 }
 
 int launch_conv32(const ConvW32& c, const float* x, int N, int H, int W, float* y, const float* res, bool relu,
@@ -799,18 +809,11 @@ int launch_conv_f8(const cbw_kws* h, const ConvF8& c, const uint8_t* x, int N, i
     if (Ho_out) *Ho_out = a.Ho;
     if (Wo_out) *Wo_out = a.Wo;
     if (!cbw_conv_fp8_supported(a)) return fail(CBW_ERR_INVALID, "fp8 conv shape not supported");
-    const bool rec = prof && prof->on && (size_t)(2 * prof->used + 1) < prof->ev.size();
-    if (rec) HIPCHK(hipEventRecord(prof->ev[2 * prof->used], st));
+    int slot;
+    CHK(Prof::begin(prof, st, &slot));
     cbw_last_conv_kernel = "?";
     HIPCHK(cbw_conv_fp8(a, st));
-    if (rec) {
-        HIPCHK(hipEventRecord(prof->ev[2 * prof->used + 1], st));
-        prof->flop[prof->used] = 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW;
-        prof->tier[prof->used] = prof->cur_tier;
-        prof->kern[prof->used] = cbw_last_conv_kernel;
-        prof->used++;
-    }
-    return CBW_OK;
+    return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel);
 }
 
 // activation sizes of one chunk through the network (elements)
@@ -1069,8 +1072,8 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
                 // stage-1 block as one fused kernel (bottleneck.hip): the identity blocks, and the first block with
                 // its shortcut folded into the expand
                 uint16_t* yo = at(y, H, W, 256);
-                const bool rec = h->prof.on && (size_t)(2 * h->prof.used + 1) < h->prof.ev.size();
-                if (rec) HIPCHK(hipEventRecord(h->prof.ev[2 * h->prof.used], st));
+                int slot;
+                CHK(Prof::begin(&h->prof, st, &slot));
                 if (s1_first)
                     HIPCHK(cbw_bottleneck_s1_first(xo, yo, b.conv[0].w.as<uint16_t>(), b.conv[0].b.as<float>(),
                                                    b.conv[1].w.as<uint16_t>(), b.conv[1].b.as<float>(),
@@ -1081,15 +1084,10 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
                                              b.conv[1].w.as<uint16_t>(), b.conv[1].b.as<float>(),
                                              b.conv[2].w.as<uint16_t>(), b.conv[2].b.as<float>(), h->zero.p, nn, H, W,
                                              st));
-                if (rec) {
-                    HIPCHK(hipEventRecord(h->prof.ev[2 * h->prof.used + 1], st));
-                    const double cin = s1_first ? 64.0 : 256.0;
-                    h->prof.flop[h->prof.used] =
-                        2.0 * nn * H * W * (cin * 64 + 64.0 * 576 + 64.0 * 256 + (s1_first ? 64.0 * 256 : 0.0));
-                    h->prof.tier[h->prof.used] = h->prof.cur_tier;
-                    h->prof.kern[h->prof.used] = s1_first ? "bottleneck_kernel<64>" : "bottleneck_ring_kernel";
-                    h->prof.used++;
-                }
+                const double cin = s1_first ? 64.0 : 256.0;
+                CHK(Prof::end(&h->prof, slot, st,
+                              2.0 * nn * H * W * (cin * 64 + 64.0 * 576 + 64.0 * 256 + (s1_first ? 64.0 * 256 : 0.0)),
+                              s1_first ? "bottleneck_kernel<64>" : "bottleneck_ring_kernel"));
             } else if (b.nconv == 3) {
                 const auto &c0 = b.conv[0], &c1 = b.conv[1], &c2 = b.conv[2];
                 const int h1 = (H + 2 * (c0.k / 2) - c0.k) / c0.stride + 1, w1 = (W + 2 * (c0.k / 2) - c0.k) / c0.stride + 1;
@@ -1149,19 +1147,13 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
         uint8_t* cur = (uint8_t*)y;
         uint8_t* other = (uint8_t*)x;
         if (q8) {
-            // the same per-launch event / FLOP / tier record blocks() makes for every fused stage-1 block
-            const bool rec = h->prof.on && (size_t)(2 * h->prof.used + 1) < h->prof.ev.size();
-            if (rec) HIPCHK(hipEventRecord(h->prof.ev[2 * h->prof.used], st));
+            int slot;
+            CHK(Prof::begin(&h->prof, st, &slot));
             HIPCHK(cbw_bottleneck_s1_q8(x, cur, b1.conv[0].w.as<uint16_t>(), b1.conv[0].b.as<float>(),
                                         b1.conv[1].w.as<uint16_t>(), b1.conv[1].b.as<float>(), b1.conv[2].w.as<uint16_t>(),
                                         b1.conv[2].b.as<float>(), 1.f / h->f8_in_scale, kc, H, W, st));
-            if (rec) {
-                HIPCHK(hipEventRecord(h->prof.ev[2 * h->prof.used + 1], st));
-                h->prof.flop[h->prof.used] = 2.0 * kc * H * W * (256.0 * 64 + 64.0 * 576 + 64.0 * 256);
-                h->prof.tier[h->prof.used] = h->prof.cur_tier;
-                h->prof.kern[h->prof.used] = "bottleneck_ring_kernel (e4m3 out)";
-                h->prof.used++;
-            }
+            CHK(Prof::end(&h->prof, slot, st, 2.0 * kc * H * W * (256.0 * 64 + 64.0 * 576 + 64.0 * 256),
+                          "bottleneck_ring_kernel (e4m3 out)"));
             C = 256;
         } else {
             HIPCHK(cbw_quant_fp8(x, cur, (int64_t)kc * H * W * C, 1.f / h->f8_in_scale, st));
@@ -1198,6 +1190,44 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
     HIPCHK(cbw_pool_fc(x, h->fc_w.as<float>(), h->fc_b16.as<float>(), logits, kc, H * W, C, st));
     return CBW_OK;
 }
+
+// The chunk loop of the scoring entry points: maps [0, n) in chunks of `chunk`, chunk i on ChunkStreams' stream and
+// workspace slot i % n.  Per chunk, in this order on its stream: fill(p0, pc, maps, stream) writes the NHWC maps of
+// [p0, p0 + pc) into the slot, the optional fp32 copy goes to features [n][L][Tk][Tu], then the network writes
+// logits [n][2].  The callers have validated everything but the workspace size.
+extern "C++" {
+template <class Fill>
+int score_chunks(cbw_kws* h, int n, int Tk, int Tu, float* logits, float* features, int chunk, void* ws,
+                 int64_t ws_bytes, hipStream_t st, bool fp8, Fill fill) {
+    const int L = h->cfg.n_layers;
+    const KwsPlan plan = kws_plan(h, Tk, Tu, chunk);
+    const int64_t per = chunk_ws_bytes(h, Tk, Tu, chunk);
+    if (ws_bytes < kws_streams() * per) return fail(CBW_ERR_OOM, "score workspace too small");
+    ChunkStreams cs(h, st, (n + chunk - 1) / chunk);
+    CHK(cs.begin());
+    for (int p0 = 0, i = 0; p0 < n; p0 += chunk, ++i) {
+        const int pc = std::min(chunk, n - p0);
+        hipStream_t s = cs.stream(i);
+        char* w = (char*)ws + cs.slot(i) * per;
+        CHK(fill(p0, pc, (uint16_t*)w, s));
+        if (features) HIPCHK(cbw_sim_to_nchw((uint16_t*)w, features + (size_t)p0 * L * Tk * Tu, pc, L, Tk, Tu, s));
+        CHK(resnet_chunk(h, plan, w, pc, Tk, Tu, logits + (size_t)p0 * 2, s, fp8));
+    }
+    return cs.end();
+}
+
+// fill for one utterance against keywords [p0, p0 + pc) (cbw_kws_score, cbw_kws_score_fp8)
+auto sim_maps_fill(const cbw_kws* h, const uint16_t* utt, const float* utt_mask, const uint16_t* kwd,
+                   const float* kwd_mask, int Tk, int Tu) {
+    const int L = h->cfg.n_layers;
+    const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
+    return [=](int p0, int pc, uint16_t* maps, hipStream_t s) -> int {
+        HIPCHK(cbw_sim_maps(kwd + (size_t)p0 * L * Tk * E, kwd_mask + (size_t)p0 * L * Tk, utt, utt_mask, maps, pc, L,
+                            Tk, Tu, E, s));
+        return CBW_OK;
+    };
+}
+}  // extern "C++"
 }  // namespace
 
 int cbw_kws_score(cbw_kws* h, const uint16_t* utt, const float* utt_mask, const uint16_t* kwd, const float* kwd_mask,
@@ -1207,26 +1237,8 @@ int cbw_kws_score(cbw_kws* h, const uint16_t* utt, const float* utt_mask, const 
     if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
     if (K == 0) return CBW_OK;
     if (K < 0 || Tk < 7 || Tu < 7 || chunk <= 0) return fail(CBW_ERR_INVALID, "bad K/Tk/Tu/chunk");
-    if (ws_bytes < cbw_kws_workspace_bytes(h, Tk, Tu, chunk)) return fail(CBW_ERR_OOM, "score workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int L = h->cfg.n_layers;
-    const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
-    const KwsPlan plan = kws_plan(h, Tk, Tu, chunk);
-    const int64_t per = chunk_ws_bytes(h, Tk, Tu, chunk);
-    ChunkStreams cs(h, st, (K + chunk - 1) / chunk);
-    CHK(cs.begin());
-    for (int k0 = 0, i = 0; k0 < K; k0 += chunk, ++i) {
-        const int kc = std::min(chunk, K - k0);
-        hipStream_t s = cs.stream(i);
-        char* w = (char*)ws + cs.slot(i) * per;
-        uint16_t* maps = (uint16_t*)w;
-        const uint16_t* kc_kwd = kwd + (size_t)k0 * L * Tk * E;
-        const float* kc_mask = kwd_mask + (size_t)k0 * L * Tk;
-        HIPCHK(cbw_sim_maps(kc_kwd, kc_mask, utt, utt_mask, maps, kc, L, Tk, Tu, E, s));
-        if (features) HIPCHK(cbw_sim_to_nchw(maps, features + (size_t)k0 * L * Tk * Tu, kc, L, Tk, Tu, s));
-        CHK(resnet_chunk(h, plan, w, kc, Tk, Tu, logits + (size_t)k0 * 2, s));
-    }
-    return cs.end();
+    return score_chunks(h, K, Tk, Tu, logits, features, chunk, ws, ws_bytes, (hipStream_t)stream, false,
+                        sim_maps_fill(h, utt, utt_mask, kwd, kwd_mask, Tk, Tu));
 }
 
 int cbw_kws_score_pairs(cbw_kws* h, const uint16_t* utt, const float* utt_mask, int B, const uint16_t* kwd,
@@ -1242,25 +1254,15 @@ int cbw_kws_score_pairs(cbw_kws* h, const uint16_t* utt, const float* utt_mask, 
         return fail(CBW_ERR_INVALID, "pair_utt and pair_kwd must both be given or both be null");
     if (!pair_utt && (int64_t)P != (int64_t)B * K)
         return fail(CBW_ERR_INVALID, "without index arrays P must be B * K (every utterance against every keyword)");
-    if (ws_bytes < cbw_kws_workspace_bytes(h, Tk, Tu, chunk)) return fail(CBW_ERR_OOM, "score workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     const int L = h->cfg.n_layers;
     const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
-    const KwsPlan plan = kws_plan(h, Tk, Tu, chunk);
-    const int64_t per = chunk_ws_bytes(h, Tk, Tu, chunk);
-    ChunkStreams cs(h, st, (P + chunk - 1) / chunk);
-    CHK(cs.begin());
-    for (int p0 = 0, i = 0; p0 < P; p0 += chunk, ++i) {
-        const int pc = std::min(chunk, P - p0);
-        hipStream_t s = cs.stream(i);
-        char* w = (char*)ws + cs.slot(i) * per;
-        uint16_t* maps = (uint16_t*)w;
-        HIPCHK(cbw_sim_maps_pairs(kwd, kwd_mask, K, utt, utt_mask, B, pair_utt ? pair_utt + p0 : nullptr,
-                                  pair_kwd ? pair_kwd + p0 : nullptr, p0, maps, pc, L, Tk, Tu, E, s));
-        if (features) HIPCHK(cbw_sim_to_nchw(maps, features + (size_t)p0 * L * Tk * Tu, pc, L, Tk, Tu, s));
-        CHK(resnet_chunk(h, plan, w, pc, Tk, Tu, logits + (size_t)p0 * 2, s));
-    }
-    return cs.end();
+    return score_chunks(h, P, Tk, Tu, logits, features, chunk, ws, ws_bytes, (hipStream_t)stream, false,
+                        [=](int p0, int pc, uint16_t* maps, hipStream_t s) -> int {
+                            HIPCHK(cbw_sim_maps_pairs(kwd, kwd_mask, K, utt, utt_mask, B,
+                                                      pair_utt ? pair_utt + p0 : nullptr,
+                                                      pair_kwd ? pair_kwd + p0 : nullptr, p0, maps, pc, L, Tk, Tu, E, s));
+                            return CBW_OK;
+                        });
 }
 
 int cbw_kws_score_fp8(cbw_kws* h, const uint16_t* utt, const float* utt_mask, const uint16_t* kwd,
@@ -1271,29 +1273,9 @@ int cbw_kws_score_fp8(cbw_kws* h, const uint16_t* utt, const float* utt_mask, co
     if (h->blocks8.empty() || h->f8_first < 0) return fail(CBW_ERR_STATE, "fp8 tier not calibrated (cbw_kws_calibrate_fp8)");
     if (K == 0) return CBW_OK;
     if (K < 0 || Tk < 7 || Tu < 7 || chunk <= 0) return fail(CBW_ERR_INVALID, "bad K/Tk/Tu/chunk");
-    if (ws_bytes < cbw_kws_workspace_bytes(h, Tk, Tu, chunk)) return fail(CBW_ERR_OOM, "score workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int L = h->cfg.n_layers;
-    const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
-    const KwsPlan plan = kws_plan(h, Tk, Tu, chunk);
-    const int64_t per = chunk_ws_bytes(h, Tk, Tu, chunk);
-    ChunkStreams cs(h, st, (K + chunk - 1) / chunk);
-    CHK(cs.begin());
-    const int tier0 = h->prof.cur_tier;
-    h->prof.cur_tier = 2;
-    int rc = CBW_OK;
-    for (int k0 = 0, i = 0; k0 < K && rc == CBW_OK; k0 += chunk, ++i) {
-        const int kc = std::min(chunk, K - k0);
-        hipStream_t s = cs.stream(i);
-        char* w = (char*)ws + cs.slot(i) * per;
-        const hipError_t e = cbw_sim_maps(kwd + (size_t)k0 * L * Tk * E, kwd_mask + (size_t)k0 * L * Tk, utt, utt_mask,
-                                          (uint16_t*)w, kc, L, Tk, Tu, E, s);
-        if (e != hipSuccess) { rc = fail(CBW_ERR_HIP, hipGetErrorString(e)); break; }
-        rc = resnet_chunk(h, plan, w, kc, Tk, Tu, logits + (size_t)k0 * 2, s, true);
-    }
-    h->prof.cur_tier = tier0;
-    CHK(rc);
-    return cs.end();
+    const TierScope tier(h->prof, 2);   // this call's profile records are the fp8 tier's
+    return score_chunks(h, K, Tk, Tu, logits, nullptr, chunk, ws, ws_bytes, (hipStream_t)stream, true,
+                        sim_maps_fill(h, utt, utt_mask, kwd, kwd_mask, Tk, Tu));
 }
 
 int cbw_kws_set_score_offset_fp8(cbw_kws* h, const float* offset) {
@@ -1360,24 +1342,14 @@ int cbw_kws_classify(cbw_kws* h, const float* maps_nchw, int K, int Tk, int Tu, 
     if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
     if (K == 0) return CBW_OK;
     if (K < 0 || Tk < 7 || Tu < 7 || chunk <= 0) return fail(CBW_ERR_INVALID, "bad K/Tk/Tu/chunk");
-    if (ws_bytes < cbw_kws_workspace_bytes(h, Tk, Tu, chunk)) return fail(CBW_ERR_OOM, "score workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     const int L = h->cfg.n_layers;
-    const KwsPlan plan = kws_plan(h, Tk, Tu, chunk);
-    const int64_t per = chunk_ws_bytes(h, Tk, Tu, chunk);
-    ChunkStreams cs(h, st, (K + chunk - 1) / chunk);
-    CHK(cs.begin());
-    for (int k0 = 0, i = 0; k0 < K; k0 += chunk, ++i) {
-        const int kc = std::min(chunk, K - k0);
-        hipStream_t s = cs.stream(i);
-        char* w = (char*)ws + cs.slot(i) * per;
-        if (stem_channels(L) == 16)
-            HIPCHK(cbw_nchw_to_nhwc16(maps_nchw + (size_t)k0 * L * Tk * Tu, (uint16_t*)w, kc, L, Tk, Tu, s));
-        else
-            HIPCHK(cbw_nchw_to_nhwc4(maps_nchw + (size_t)k0 * L * Tk * Tu, (uint16_t*)w, kc, L, Tk, Tu, s));
-        CHK(resnet_chunk(h, plan, w, kc, Tk, Tu, logits + (size_t)k0 * 2, s));
-    }
-    return cs.end();
+    return score_chunks(h, K, Tk, Tu, logits, nullptr, chunk, ws, ws_bytes, (hipStream_t)stream, false,
+                        [=](int p0, int pc, uint16_t* maps, hipStream_t s) -> int {
+                            const float* src = maps_nchw + (size_t)p0 * L * Tk * Tu;
+                            if (stem_channels(L) == 16) HIPCHK(cbw_nchw_to_nhwc16(src, maps, pc, L, Tk, Tu, s));
+                            else HIPCHK(cbw_nchw_to_nhwc4(src, maps, pc, L, Tk, Tu, s));
+                            return CBW_OK;
+                        });
 }
 
 // ---- CB-Whisper original spotter (cb_whisper.py:93-129, :189-210)

@@ -138,6 +138,47 @@ def test_profile_records_of_a_chained_chunk(monkeypatch):
     assert not any(k.startswith("conv_stream_chain_kernel") for k in got["0"][2])
 
 
+def test_profile_records_across_entry_points():
+    """One profile session over four calls on the same 3 keywords in one chunk: cbw_kws_score, cbw_kws_score_pairs
+    (B = 1, pair p = (0, p)), cbw_kws_score_fp8, cbw_kws_score again.  The pair call runs the same network launches as
+    the single-utterance call, so its records match in count, kernel names and FLOPs; the fp8 call's records all carry
+    tier 2, and the bf16 call after it tier 0 again (cbw_kws_profile starts the session at tier 0)."""
+    import ctypes
+    s = _engine("resnet-50")
+    eng, lib = s["eng"], _lib.load()
+    K, CAP = 3, 256
+    pk, pkm = s["pk"][:K].contiguous(), s["pkm"][:K].contiguous()
+    pk32, _ = eng.project_f32(s["kwd"][:K], s["km"][:K])
+    pu32, _ = eng.project_f32(s["utt"], s["um"])
+    eng.calibrate_fp8(pu32[0], s["pum"], pk32, pkm, margin=1.0, utt=s["pu"], kwd=pk)
+    _lib.check(lib.cbw_kws_profile(eng.h, CAP), "cbw_kws_profile")
+    calls = [lambda: eng.score(s["pu"], s["pum"], pk, pkm, chunk=K),
+             lambda: eng.score_pairs(s["pu"][None], s["pum"][None], pk, pkm, [0] * K, list(range(K)), chunk=K),
+             lambda: eng.score_fp8(s["pu"], s["pum"], pk, pkm, chunk=K),
+             lambda: eng.score(s["pu"], s["pum"], pk, pkm, chunk=K)]
+    marks = [0]
+    for call in calls:
+        call()
+        marks.append(lib.cbw_kws_profile_tiers(eng.h, None, 0))
+    torch.cuda.synchronize()
+    st, en, fl = (np.zeros(CAP) for _ in range(3))
+    tiers = np.full(CAP, -1, np.int32)
+    names = (ctypes.c_char_p * CAP)()
+    n = lib.cbw_kws_profile_records(eng.h, st.ctypes.data, en.ctypes.data, fl.ctypes.data, CAP)
+    lib.cbw_kws_profile_tiers(eng.h, tiers.ctypes.data, CAP)
+    lib.cbw_kws_profile_kernels(eng.h, names, CAP)
+    lib.cbw_kws_profile(eng.h, 0)
+    assert marks[-1] == n < CAP   # nothing dropped for want of room
+    rec = [([(names[i] or b"").decode() for i in range(a, b)], fl[a:b].tolist(), tiers[a:b].tolist())
+           for a, b in zip(marks[:-1], marks[1:])]
+    score, pairs, fp8, again = rec
+    assert len(score[0]) > 0 and all(f > 0 for f in score[1])
+    assert len(pairs[0]) == len(score[0]) and pairs[0] == score[0] and pairs[1] == score[1]
+    assert set(score[2]) == {0} and set(pairs[2]) == {0}
+    assert len(fp8[0]) > 0 and set(fp8[2]) == {2}
+    assert again[0] == score[0] and again[1] == score[1] and set(again[2]) == {0}
+
+
 def test_untouched_paths_still_run():
     """ResNet-34 (basic blocks: nothing to chain) and the fp8 tier (its stage-2 blocks are e4m3 convs) with the
     default settings."""

@@ -163,6 +163,27 @@ def test_kwsmodel_forward_paired_batch(batch):
         m.forward(kwd_features=kwd, utt_features=utt[:2], kwd_mask=km, utt_mask=um[:2])
 
 
+def test_score_checks_mask_shapes(batch):
+    """``score`` refuses a mask that does not cover its features before anything is launched (the kernel would read
+    past its end), and takes the utterance with or without the batch axis of 1."""
+    eng, pu, pum, pk, pkm = engine("LEF64-r18", batch)
+    Tk, Tu = pk.shape[2], pu.shape[2]
+    sentinel = 123.0
+    buf = torch.full((K, 2), sentinel, device=eng.device)
+    with pytest.raises(ValueError):   # kwd_mask [K, L, Tk - 1]
+        eng.score(pu[0], pum[0], pk, pkm[:, :, :Tk - 1], chunk=CHUNK, logits_out=buf)
+    for bad in (pum[0][:, :Tu - 1], pum[:2], pum[0].reshape(-1)[:L * Tu - 1]):   # not L * Tu elements
+        with pytest.raises(ValueError):
+            eng.score(pu[0], bad, pk, pkm, chunk=CHUNK, logits_out=buf)
+    torch.cuda.synchronize()
+    assert bool((buf == sentinel).all())
+    ref = eng.score(pu[0], pum[0], pk, pkm, chunk=CHUNK)
+    assert tuple(pu[:1].shape) == (1, L, Tu, 64) and tuple(pum[:1].shape) == (1, L, Tu)
+    assert torch.equal(eng.score(pu[:1], pum[:1], pk, pkm, chunk=CHUNK), ref)
+    assert torch.equal(eng.score(pu[0], pum[0].reshape(-1), pk, pkm, chunk=CHUNK), ref)   # L * Tu elements: reshaped
+    assert torch.isfinite(ref).all()
+
+
 def test_argument_handling(batch):
     from cbw import _lib
     eng, pu, pum, pk, pkm = engine("LEF64-r18", batch)
