@@ -181,12 +181,26 @@ class KwsEngine:
                 _lib.check(self.lib.cbw_kws_calibrate_bias(self.h, None, None, None, None, 0, 1, 1, None, 0, None, 0,
                                                            _lib.stream_handle()), "cbw_kws_calibrate_bias")
             return
+        utt32, utt_mask, sel, ws = self._calibration_inputs("calibrate_bias", utt32, utt_mask, kwd32, sel)
+        K, _, Tk, _ = kwd32.shape
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cbw_kws_calibrate_bias(
+                self.h, utt32.contiguous().data_ptr(), utt_mask.to(torch.float32).contiguous().data_ptr(),
+                kwd32.contiguous().data_ptr(), kwd_mask.to(torch.float32).contiguous().data_ptr(), K, Tk,
+                utt32.shape[1], sel.data_ptr(), sel.numel(), ws.data_ptr(), ws.numel(), _lib.stream_handle()),
+                "cbw_kws_calibrate_bias")
+        return self._calibrate_offset(self.score, "cbw_kws_set_score_offset", utt32, utt_mask, kwd32, kwd_mask, sel,
+                                      utt, kwd)
+
+    def _calibration_inputs(self, what: str, utt32, utt_mask, kwd32, sel):
+        """Prologue of calibrate_bias / calibrate_fp8: the utterance without its batch axis of 1, the fp32 check,
+        ``sel`` (default: every keyword) on the device and range-checked, the re-scoring workspace."""
         if utt32.dim() == 4:
             utt32, utt_mask = utt32[0], utt_mask.reshape(utt_mask.shape[-2:])
         K, L, Tk, E = kwd32.shape
         Tu = utt32.shape[1]
         if utt32.dtype != torch.float32 or kwd32.dtype != torch.float32 or tuple(utt32.shape) != (L, Tu, E):
-            raise ValueError("calibrate_bias takes the fp32 projections (KwsEngine.project_f32)")
+            raise ValueError(f"{what} takes the fp32 projections (KwsEngine.project_f32)")
         if sel is None:
             sel = torch.arange(K, dtype=torch.int32, device=self.device)
         sel = sel.to(self.device, torch.int32).contiguous()
@@ -195,27 +209,28 @@ class KwsEngine:
         with torch.cuda.device(self.device):
             nb = self.lib.cbw_kws_rescore_workspace_bytes(self.h, Tk, Tu)
             if nb < 0:
-                _lib.check(-4, "cbw_kws_calibrate_bias workspace")
-            ws = self._ws_rescore.get(nb, self.device)
-            _lib.check(self.lib.cbw_kws_calibrate_bias(
-                self.h, utt32.contiguous().data_ptr(), utt_mask.to(torch.float32).contiguous().data_ptr(),
-                kwd32.contiguous().data_ptr(), kwd_mask.to(torch.float32).contiguous().data_ptr(), K, Tk, Tu,
-                sel.data_ptr(), sel.numel(), ws.data_ptr(), ws.numel(), _lib.stream_handle()), "cbw_kws_calibrate_bias")
+                _lib.check(-4, f"cbw_kws_{what} workspace")
+            return utt32, utt_mask, sel, self._ws_rescore.get(nb, self.device)
+
+    def _calibrate_offset(self, score, setter: str, utt32, utt_mask, kwd32, kwd_mask, sel, utt, kwd):
+        """Tail of calibrate_bias / calibrate_fp8: with the bf16 projections of the calibration pairs, zero the
+        tier's logit offset, score the pairs with ``score``, re-score them in fp32 and set (and return) the mean
+        difference as the offset; None without them."""
         if utt is None or kwd is None:
             return None
+        set_offset = getattr(self.lib, setter)
         zero = np.zeros(2, np.float32)
-        _lib.check(self.lib.cbw_kws_set_score_offset(self.h, zero.ctypes.data), "cbw_kws_set_score_offset")
+        _lib.check(set_offset(self.h, zero.ctypes.data), setter)
         if utt.dim() == 4:
             utt = utt[0]
         s_l = sel.long()
         km = kwd_mask[s_l].contiguous()
-        l16 = self.score(utt, utt_mask, kwd[s_l].contiguous(), km)
-        l32 = l16.clone()
+        low = score(utt, utt_mask, kwd[s_l].contiguous(), km)
+        l32 = torch.empty_like(low)
         self.rescore(utt32, utt_mask, kwd32[s_l].contiguous(), km, l32,
                      torch.arange(sel.numel(), dtype=torch.int32, device=self.device), trusted=True)
-        off = (l32.double() - l16.double()).mean(0).cpu().numpy().astype(np.float32)
-        _lib.check(self.lib.cbw_kws_set_score_offset(self.h, np.ascontiguousarray(off).ctypes.data),
-                   "cbw_kws_set_score_offset")
+        off = (l32.double() - low.double()).mean(0).cpu().numpy().astype(np.float32)
+        _lib.check(set_offset(self.h, np.ascontiguousarray(off).ctypes.data), setter)
         return off
 
     # ------------------------------------------------------------------ fp8 first tier
@@ -227,41 +242,16 @@ class KwsEngine:
         amax * margin / 448 and the weights are quantized against it.  With the bf16 projections of the same pairs
         (``utt`` [L, Tu, E], ``kwd`` [K, L, Tk, E]) the mean fp32 - fp8 logit difference is then moved into the fp8
         pass's classifier bias (cbw_kws_set_score_offset_fp8) and returned.  Setup-time (synchronises)."""
-        if utt32.dim() == 4:
-            utt32, utt_mask = utt32[0], utt_mask.reshape(utt_mask.shape[-2:])
-        K, L, Tk, E = kwd32.shape
-        Tu = utt32.shape[1]
-        if sel is None:
-            sel = torch.arange(K, dtype=torch.int32, device=self.device)
-        sel = sel.to(self.device, torch.int32).contiguous()
-        if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= K:
-            raise ValueError("calibration pairs out of range")
+        utt32, utt_mask, sel, ws = self._calibration_inputs("calibrate_fp8", utt32, utt_mask, kwd32, sel)
+        K, _, Tk, _ = kwd32.shape
         with torch.cuda.device(self.device):
-            nb = self.lib.cbw_kws_rescore_workspace_bytes(self.h, Tk, Tu)
-            if nb < 0:
-                _lib.check(-4, "cbw_kws_calibrate_fp8 workspace")
-            ws = self._ws_rescore.get(nb, self.device)
             _lib.check(self.lib.cbw_kws_calibrate_fp8(
                 self.h, utt32.contiguous().data_ptr(), utt_mask.to(torch.float32).contiguous().data_ptr(),
-                kwd32.contiguous().data_ptr(), kwd_mask.to(torch.float32).contiguous().data_ptr(), K, Tk, Tu,
-                sel.data_ptr(), sel.numel(), float(margin), ws.data_ptr(), ws.numel(), _lib.stream_handle()),
-                "cbw_kws_calibrate_fp8")
-        if utt is None or kwd is None:
-            return None
-        zero = np.zeros(2, np.float32)
-        _lib.check(self.lib.cbw_kws_set_score_offset_fp8(self.h, zero.ctypes.data), "cbw_kws_set_score_offset_fp8")
-        if utt.dim() == 4:
-            utt = utt[0]
-        s_l = sel.long()
-        km = kwd_mask[s_l].contiguous()
-        l8 = self.score_fp8(utt, utt_mask, kwd[s_l].contiguous(), km)
-        l32 = torch.empty_like(l8)
-        self.rescore(utt32, utt_mask, kwd32[s_l].contiguous(), km, l32,
-                     torch.arange(sel.numel(), dtype=torch.int32, device=self.device), trusted=True)
-        off = (l32.double() - l8.double()).mean(0).cpu().numpy().astype(np.float32)
-        _lib.check(self.lib.cbw_kws_set_score_offset_fp8(self.h, np.ascontiguousarray(off).ctypes.data),
-                   "cbw_kws_set_score_offset_fp8")
-        return off
+                kwd32.contiguous().data_ptr(), kwd_mask.to(torch.float32).contiguous().data_ptr(), K, Tk,
+                utt32.shape[1], sel.data_ptr(), sel.numel(), float(margin), ws.data_ptr(), ws.numel(),
+                _lib.stream_handle()), "cbw_kws_calibrate_fp8")
+        return self._calibrate_offset(self.score_fp8, "cbw_kws_set_score_offset_fp8", utt32, utt_mask, kwd32, kwd_mask,
+                                      sel, utt, kwd)
 
     def fp8_scales(self) -> np.ndarray:
         n = self.lib.cbw_kws_fp8_scales(self.h, None, 0)

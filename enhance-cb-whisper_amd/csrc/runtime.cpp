@@ -83,6 +83,22 @@ std::vector<uint16_t> to_bf16(const std::vector<float>& v) {
     return o;
 }
 
+float bf16_round_host(float v) {
+    const uint32_t u = (uint32_t)f2bf_host(v) << 16;
+    float r;
+    std::memcpy(&r, &u, 4);
+    return r;
+}
+
+// the 3-term split of n fp32 weights: dst = [hi | lo | hi], n each, hi = bf16(v), lo = bf16(v - hi); the caller
+// places dst (row stride, zero padding behind the 3 n values)
+void split3(const float* v, int n, uint16_t* dst) {
+    for (int i = 0; i < n; ++i) {
+        dst[i] = dst[2 * n + i] = f2bf_host(v[i]);
+        dst[n + i] = f2bf_host(v[i] - bf16_round_host(v[i]));
+    }
+}
+
 struct ParamStore {
     std::map<std::string, std::vector<float>> host;
     int set(const char* name, const float* data, int64_t numel) {
@@ -120,10 +136,14 @@ int fold_bn(const ParamStore& ps, const std::string& bn, int cout, std::vector<f
     return CBW_OK;
 }
 
-struct ConvW {
-    DevBuf w, b;
+struct ConvShape {
     int cin = 0, cout = 0, k = 1, stride = 1;
     bool relu = false;
+};
+
+// a conv (or Linear: k = 1) of any tier: its shape and its device weights in that tier's format, bias fp32
+struct ConvW : ConvShape {
+    DevBuf w, b;
 };
 
 // torch conv weight [Cout][Cin][k][k] + BN -> f32 [Cout][k][k][Cin] (BN scale folded) + f32 bias
@@ -145,10 +165,12 @@ int fold_conv_host(const ParamStore& ps, const std::string& prefix, int cin, int
     return CBW_OK;
 }
 
-int load_conv_bn(const ParamStore& ps, const std::string& prefix, ConvW& c) {
+// conv `prefix` of shape s with BN folded: bf16 weights, or fp32 ones for the exact re-scoring path (kws_exact.hip)
+int load_conv_bn(const ParamStore& ps, const std::string& prefix, const ConvShape& s, ConvW& c, bool f32 = false) {
     std::vector<float> o, sh;
-    CHK(fold_conv_host(ps, prefix, c.cin, c.cout, c.k, o, sh));
-    CHK(c.w.upload(to_bf16(o)));
+    CHK(fold_conv_host(ps, prefix, s.cin, s.cout, s.k, o, sh));
+    static_cast<ConvShape&>(c) = s;
+    CHK(f32 ? c.w.upload(o) : c.w.upload(to_bf16(o)));
     CHK(c.b.upload(sh));
     return CBW_OK;
 }
@@ -217,21 +239,28 @@ struct Src2 {   // second K-source of a fused 1x1 conv (ConvArgs::x2)
     int cin, H, W, stride;
 };
 
+// output extent of a k-tap, "same"-padded (k / 2) conv or pool over h; k = 1: a strided 1x1 (the shortcuts)
+int out_dim(int h, int k, int stride) { return (h + 2 * (k / 2) - k) / stride + 1; }
+
+// the geometry fields ConvArgs, F32ConvArgs and F8ConvArgs share, for conv c over x [N][H][W][c.cin]
+template <class Args>
+void conv_geometry(Args& a, const ConvShape& c, int N, int H, int W) {
+    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout; a.KH = a.KW = c.k;
+    a.sh = a.sw = c.stride; a.ph = a.pw = c.k / 2;
+    a.Ho = out_dim(H, c.k, c.stride);
+    a.Wo = out_dim(W, c.k, c.stride);
+    a.M = N * a.Ho * a.Wo;
+}
+
 int launch_conv(const ConvW& c, const void* x, int N, int H, int W, void* y, const void* res, int flags,
-                const void* zero, hipStream_t st, int* Ho_out = nullptr, int* Wo_out = nullptr, Prof* prof = nullptr,
-                const Src2* src2 = nullptr, float* splitk_ws = nullptr) {
+                const void* zero, hipStream_t st, Prof* prof = nullptr, const Src2* src2 = nullptr,
+                float* splitk_ws = nullptr) {
     ConvArgs a{};
     a.x = x; a.w = c.w.p; a.bias = c.b.as<float>(); a.res = res; a.y = y; a.zero = zero;
     if (src2) { a.x2 = src2->x; a.Cin2 = src2->cin; a.H2 = src2->H; a.W2 = src2->W; a.s2 = src2->stride; }
-    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout; a.KH = c.k; a.KW = c.k;
-    a.sh = a.sw = c.stride; a.ph = a.pw = c.k / 2;
-    a.Ho = (H + 2 * a.ph - a.KH) / a.sh + 1;
-    a.Wo = (W + 2 * a.pw - a.KW) / a.sw + 1;
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, c, N, H, W);
     a.res_ld = a.y_ld = c.cout;
     a.flags = flags | (c.relu ? CBW_EPI_RELU : 0);
-    if (Ho_out) *Ho_out = a.Ho;
-    if (Wo_out) *Wo_out = a.Wo;
     int slot;
     CHK(Prof::begin(prof, st, &slot));
     cbw_last_conv_kernel = "?";
@@ -278,6 +307,77 @@ size_t align_up(size_t n) { return (n + 255) & ~(size_t)255; }
 // embedding 64, stages [256,512,1024,2048]x[3,4,6,3] bottleneck (resnet-50),
 // [64,128,256,512] basic for resnet-18/34; stride 2 in the first layer of stages
 // 2-4, in the 3x3 (downsample_in_bottleneck = False); shortcut when shape changes.
+// One block of the network as the reference builds it; relu is the conv module's own activation (the block's
+// ReLU after the residual sum is the tiers' business).  cbw_kws_finalize builds the list once (cbw_kws::topo) and
+// every tier's loader, walker and planner reads it.
+struct BlockTopo {
+    std::string prefix;   // parameter prefix of the block
+    int stage = 0;        // 1..4
+    int nconv = 0;        // 3 bottleneck, 2 basic
+    ConvShape conv[3];
+    bool has_sc = false;  // projection shortcut (1x1, the block's stride)
+    ConvShape sc;
+};
+
+int resnet_topology(int depth, std::vector<BlockTopo>& topo) {
+    std::vector<int> hs, depths;
+    bool bottleneck = true;
+    switch (depth) {
+        case 50: hs = {256, 512, 1024, 2048}; depths = {3, 4, 6, 3}; break;
+        case 34: hs = {64, 128, 256, 512}; depths = {3, 4, 6, 3}; bottleneck = false; break;
+        case 18: hs = {64, 128, 256, 512}; depths = {2, 2, 2, 2}; bottleneck = false; break;
+        default: return fail(CBW_ERR_INVALID, "resnet_depth must be 18, 34 or 50");
+    }
+    topo.clear();
+    int cin = 64;
+    for (size_t s = 0; s < hs.size(); ++s) {
+        const int cout = hs[s];
+        for (int li = 0; li < depths[s]; ++li) {
+            const int stride = (li == 0 && s > 0) ? 2 : 1;
+            BlockTopo b;
+            b.prefix = "model.feature_extractor.encoder.stages." + std::to_string(s) + ".layers." + std::to_string(li);
+            b.stage = (int)s + 1;
+            b.has_sc = cin != cout || stride != 1;
+            if (b.has_sc) b.sc = {cin, cout, 1, stride, false};
+            if (bottleneck) {
+                const int mid = cout / 4;
+                b.nconv = 3;
+                b.conv[0] = {cin, mid, 1, 1, true};
+                b.conv[1] = {mid, mid, 3, stride, true};
+                b.conv[2] = {mid, cout, 1, 1, false};
+            } else {
+                b.nconv = 2;
+                b.conv[0] = {cin, cout, 3, stride, true};
+                b.conv[1] = {cout, cout, 3, 1, false};
+            }
+            topo.push_back(std::move(b));
+            cin = cout;
+        }
+    }
+    return CBW_OK;
+}
+
+// the stem conv over the L map channels (the max-pool 3x3 stride 2 follows)
+ConvShape stem_shape(int L) { return {L, 64, 7, 2, true}; }
+
+// extents of a block's tensors over an H x W input: the first conv's output, the block's output (the second conv's:
+// a bottleneck's third is 1x1 stride 1) and the projection shortcut's output
+struct BlockDims {
+    int h1, w1, Ho, Wo, hs, ws;
+};
+BlockDims block_dims(const BlockTopo& b, int H, int W) {
+    BlockDims d;
+    d.h1 = out_dim(H, b.conv[0].k, b.conv[0].stride);
+    d.w1 = out_dim(W, b.conv[0].k, b.conv[0].stride);
+    d.Ho = out_dim(d.h1, b.conv[1].k, b.conv[1].stride);
+    d.Wo = out_dim(d.w1, b.conv[1].k, b.conv[1].stride);
+    d.hs = out_dim(H, 1, b.sc.stride);
+    d.ws = out_dim(W, 1, b.sc.stride);
+    return d;
+}
+
+// one block's device weights in one tier: the bf16 scoring network, the fp32 copy (BN folded in fp32, no shortcut
+// fusion) or the compensated one
 struct BlockW {
     ConvW conv[3];
     int nconv = 0;
@@ -286,15 +386,11 @@ struct BlockW {
     ConvW sc;
     DevBuf chain_w;          // conv[0]'s weights in cbw_conv_chain's fragment order (stage-2 identity blocks: the
                              // previous block's expand launch computes this block's reduce too)
-    std::string prefix;      // parameter prefix of the block (bias correction re-folds from it)
-    int stage = 0;           // 1..4
 };
 
 // e4m3 conv of the fp8 tier (conv_fp8.hip): w [Cout][k][k][Cin] e4m3 = q(w_folded * s_in / alpha), alpha [Cout]
-struct ConvF8 {
-    DevBuf w, alpha, b;
-    int cin = 0, cout = 0, k = 1, stride = 1;
-    bool relu = false;
+struct ConvF8 : ConvW {
+    DevBuf alpha;
 };
 struct BlockF8 {
     ConvF8 conv[3];
@@ -305,51 +401,18 @@ struct BlockF8 {
     bool out_bf16 = false;                                  // the network's last block: bf16 for the pool / fc
 };
 
-// fp32 copies for the exact re-scoring path (kws_exact.hip): BN folded in fp32, no shortcut fusion
-struct ConvW32 {
-    DevBuf w, b;
-    int cin = 0, cout = 0, k = 1, stride = 1;
-    bool relu = false;
-};
-struct BlockW32 {
-    ConvW32 conv[3];
-    int nconv = 0;
-    bool has_sc = false;
-    ConvW32 sc;
-};
-
-int load_conv_bn32(const ParamStore& ps, const std::string& prefix, ConvW32& c) {
-    std::vector<float> o, sh;
-    CHK(fold_conv_host(ps, prefix, c.cin, c.cout, c.k, o, sh));
-    CHK(c.w.upload(o));
-    CHK(c.b.upload(sh));
-    return CBW_OK;
-}
-
 // compensated bf16 (3-term split) copy of a conv for the middle re-scoring tier: BN folded in fp32, then
 // w [Cout][k][k][3 Cin] = [w_hi | w_lo | w_hi] (w_hi = bf16(w), w_lo = bf16(w - w_hi)) against activations
 // stored [x_hi | x_lo] (CBW_EPI_SPLIT3) and read as the K-segments [x_hi | x_hi | x_lo] (ConvArgs::xfold),
 // so one bf16 MFMA conv over 3 Cin K-channels accumulates x_hi.w_hi + x_hi.w_lo + x_lo.w_hi in fp32 (only
 // x_lo.w_lo, ~2^-16 relative, is dropped)
-int load_conv_bn_x3(const ParamStore& ps, const std::string& prefix, int cin, int cout, int k, int stride, bool relu,
-                    ConvW& c) {
+int load_conv_bn_x3(const ParamStore& ps, const std::string& prefix, const ConvShape& s, bool relu, ConvW& c) {
     std::vector<float> o, sh;
-    CHK(fold_conv_host(ps, prefix, cin, cout, k, o, sh));
-    const size_t taps = (size_t)cout * k * k;
-    std::vector<uint16_t> w(taps * 3 * cin);
-    for (size_t t = 0; t < taps; ++t)
-        for (int ci = 0; ci < cin; ++ci) {
-            const float v = o[t * cin + ci];
-            const uint16_t hi = f2bf_host(v);
-            const uint32_t u = (uint32_t)hi << 16;
-            float hv;
-            std::memcpy(&hv, &u, 4);
-            uint16_t* row = &w[t * 3 * cin];
-            row[ci] = hi;
-            row[cin + ci] = f2bf_host(v - hv);
-            row[2 * cin + ci] = hi;
-        }
-    c.cin = 3 * cin; c.cout = cout; c.k = k; c.stride = stride; c.relu = relu;
+    CHK(fold_conv_host(ps, prefix, s.cin, s.cout, s.k, o, sh));
+    const size_t taps = (size_t)s.cout * s.k * s.k;
+    std::vector<uint16_t> w(taps * 3 * s.cin);
+    for (size_t t = 0; t < taps; ++t) split3(&o[t * s.cin], s.cin, &w[t * 3 * s.cin]);
+    static_cast<ConvShape&>(c) = {3 * s.cin, s.cout, s.k, s.stride, relu};
     CHK(c.w.upload(w));
     CHK(c.b.upload(sh));
     return CBW_OK;
@@ -359,21 +422,14 @@ int load_conv_bn_x3(const ParamStore& ps, const std::string& prefix, int cin, in
 // (SPLIT3: bf16 [M][2 Cout] [hi | lo] + optional fp32 copy y32; OUT_F32: fp32 [M][Cout]); residual fp32
 // [M][Cout] (res_split false) or a [hi | lo] tensor (res_split true)
 int launch_conv_x3(const ConvW& c, const void* x, int N, int H, int W, void* y, float* y32, const void* res,
-                   bool res_split, int flags, const void* zero, hipStream_t st, int* Ho_out = nullptr,
-                   int* Wo_out = nullptr, Prof* prof = nullptr) {
+                   bool res_split, int flags, const void* zero, hipStream_t st, Prof* prof) {
     ConvArgs a{};
     a.x = x; a.w = c.w.p; a.bias = c.b.as<float>(); a.res = res; a.y = y; a.y32 = y32; a.zero = zero;
     a.xfold = c.cin / 3; a.x_ld = 2 * (c.cin / 3);
-    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout; a.KH = a.KW = c.k;
-    a.sh = a.sw = c.stride; a.ph = a.pw = c.k / 2;
-    a.Ho = (H + 2 * a.ph - a.KH) / a.sh + 1;
-    a.Wo = (W + 2 * a.pw - a.KW) / a.sw + 1;
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, c, N, H, W);
     a.res_ld = res_split ? 2 * c.cout : c.cout;
     a.y_ld = (flags & CBW_EPI_SPLIT3) ? 2 * c.cout : c.cout;
     a.flags = flags | (res ? (res_split ? CBW_EPI_RES_SPLIT : CBW_EPI_RES_F32) : 0) | (c.relu ? CBW_EPI_RELU : 0);
-    if (Ho_out) *Ho_out = a.Ho;
-    if (Wo_out) *Wo_out = a.Wo;
     int slot;
     CHK(Prof::begin(prof, st, &slot));
     cbw_last_conv_kernel = "?";
@@ -382,18 +438,12 @@ int launch_conv_x3(const ConvW& c, const void* x, int N, int H, int W, void* y, 
     return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel, 1);
 }
 
-int launch_conv32(const ConvW32& c, const float* x, int N, int H, int W, float* y, const float* res, bool relu,
-                  hipStream_t st, int* Ho_out = nullptr, int* Wo_out = nullptr) {
+int launch_conv32(const ConvW& c, const float* x, int N, int H, int W, float* y, const float* res, bool relu,
+                  hipStream_t st) {
     F32ConvArgs a{};
     a.x = x; a.w = c.w.as<float>(); a.bias = c.b.as<float>(); a.res = res; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout; a.KH = a.KW = c.k;
-    a.sh = a.sw = c.stride; a.ph = a.pw = c.k / 2;
-    a.Ho = (H + 2 * a.ph - a.KH) / a.sh + 1;
-    a.Wo = (W + 2 * a.pw - a.KW) / a.sw + 1;
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, c, N, H, W);
     a.relu = relu ? 1 : 0;
-    if (Ho_out) *Ho_out = a.Ho;
-    if (Wo_out) *Wo_out = a.Wo;
     HIPCHK(cbw_conv_f32(a, st));
     return CBW_OK;
 }
@@ -459,6 +509,7 @@ struct cbw_kws {
     bool finalized = false;
     DevBuf zero;
     DevBuf stem_w, stem_b;
+    std::vector<BlockTopo> topo;   // the network (resnet_topology); blocks, blocks32 and blocks3 run parallel to it
     std::vector<BlockW> blocks;
     int hidden = 2048;
     DevBuf fc_w, fc_b;
@@ -469,11 +520,11 @@ struct cbw_kws {
     DevBuf tp_w, tp_b;   // LEF time projector, BN folded: f32 [L][3][U][U] (k, in, out), [L][U]
     Prof prof;
     // fp32 network (exact re-scoring): stem [64][7][7][L], blocks with a separate shortcut, projector
-    ConvW32 stem32;
+    ConvW stem32;
     DevBuf stem16x3_w;   // compensated tier's stem: [64][7][8][16] bf16 = [w_hi | w_lo | w_hi | 0] (3 L <= 16)
-    std::vector<BlockW32> blocks32;
+    std::vector<BlockW> blocks32;
     std::vector<BlockW> blocks3;   // compensated bf16 (3-term split) convs of the middle re-scoring tier
-    std::vector<ConvW32> p1_32, p2_32;
+    std::vector<ConvW> p1_32, p2_32;
     // keyword chunks rotate over the caller's stream and these side streams, so one chunk's
     // partially filled launches (tile tails, the short stage-4 convs) and memory-bound layers
     // overlap another chunk's work; fork/join by events, so the whole score call stays
@@ -515,15 +566,7 @@ namespace {
 
 int build_resnet(cbw_kws* h) {
     const int L = h->cfg.n_layers;
-    std::vector<int> hs, depths;
-    bool bottleneck = true;
-    switch (h->cfg.resnet_depth) {
-        case 50: hs = {256, 512, 1024, 2048}; depths = {3, 4, 6, 3}; break;
-        case 34: hs = {64, 128, 256, 512}; depths = {3, 4, 6, 3}; bottleneck = false; break;
-        case 18: hs = {64, 128, 256, 512}; depths = {2, 2, 2, 2}; bottleneck = false; break;
-        default: return fail(CBW_ERR_INVALID, "resnet_depth must be 18, 34 or 50");
-    }
-    h->hidden = hs.back();
+    h->hidden = h->topo.back().conv[h->topo.back().nconv - 1].cout;
     const std::string root = "model.feature_extractor";
     // stem: [64][L][7][7] + BN -> bf16 [64][7][8][4]
     {
@@ -543,49 +586,28 @@ int build_resnet(cbw_kws* h) {
         CHK(h->stem_b.upload(sh));
     }
     h->blocks.clear();
-    int cin = 64;
-    for (size_t s = 0; s < hs.size(); ++s) {
-        const int cout = hs[s];
-        for (int li = 0; li < depths[s]; ++li) {
-            const int stride = (li == 0 && s > 0) ? 2 : 1;
-            const std::string p = root + ".encoder.stages." + std::to_string(s) + ".layers." + std::to_string(li);
-            BlockW b;
-            b.prefix = p;
-            b.stage = (int)s + 1;
-            if (cin != cout || stride != 1) {
-                b.has_sc = true;
-                b.sc.cin = cin; b.sc.cout = cout; b.sc.k = 1; b.sc.stride = stride; b.sc.relu = false;
-                CHK(load_conv_bn(h->ps, p + ".shortcut", b.sc));
-            }
-            if (bottleneck) {
-                const int mid = cout / 4;
-                const int ci[3] = {cin, mid, mid}, co[3] = {mid, mid, cout}, k[3] = {1, 3, 1}, st[3] = {1, stride, 1};
-                const bool rl[3] = {true, true, false};
-                b.nconv = 3;
-                for (int j = 0; j < 3; ++j) {
-                    b.conv[j].cin = ci[j]; b.conv[j].cout = co[j]; b.conv[j].k = k[j]; b.conv[j].stride = st[j];
-                    b.conv[j].relu = rl[j];
-                    if (j == 2 && b.has_sc && cout % 128 == 0 && sc_fusion_enabled()) {
-                        CHK(load_fused_expand_shortcut(h->ps, p + ".layer.2", p + ".shortcut", mid, cin, cout, b.conv[2]));
-                        b.fused_sc = true;
-                    } else {
-                        CHK(load_conv_bn(h->ps, p + ".layer." + std::to_string(j), b.conv[j]));
-                    }
-                }
-                if (!b.has_sc && cin == 512 && mid == 128) {   // the weights never change after this (bias
-                    CHK(b.chain_w.alloc((size_t)mid * cin * 2));   // calibration rewrites biases only)
-                    HIPCHK(cbw_conv_chain_pack(b.conv[0].w.as<uint16_t>(), b.chain_w.as<uint16_t>(), nullptr));
-                    HIPCHK(hipStreamSynchronize(nullptr));
-                }
+    for (const BlockTopo& t : h->topo) {
+        const int cin = t.conv[0].cin, mid = t.conv[0].cout, cout = t.conv[t.nconv - 1].cout;
+        BlockW b;
+        b.nconv = t.nconv;
+        b.has_sc = t.has_sc;
+        if (t.has_sc) CHK(load_conv_bn(h->ps, t.prefix + ".shortcut", t.sc, b.sc));
+        for (int j = 0; j < t.nconv; ++j) {
+            if (t.nconv == 3 && j == 2 && t.has_sc && cout % 128 == 0 && sc_fusion_enabled()) {
+                static_cast<ConvShape&>(b.conv[2]) = t.conv[2];
+                CHK(load_fused_expand_shortcut(h->ps, t.prefix + ".layer.2", t.prefix + ".shortcut", mid, cin, cout,
+                                               b.conv[2]));
+                b.fused_sc = true;
             } else {
-                b.nconv = 2;
-                b.conv[0].cin = cin; b.conv[0].cout = cout; b.conv[0].k = 3; b.conv[0].stride = stride; b.conv[0].relu = true;
-                b.conv[1].cin = cout; b.conv[1].cout = cout; b.conv[1].k = 3; b.conv[1].stride = 1; b.conv[1].relu = false;
-                for (int j = 0; j < 2; ++j) CHK(load_conv_bn(h->ps, p + ".layer." + std::to_string(j), b.conv[j]));
+                CHK(load_conv_bn(h->ps, t.prefix + ".layer." + std::to_string(j), t.conv[j], b.conv[j]));
             }
-            h->blocks.push_back(std::move(b));
-            cin = cout;
         }
+        if (t.nconv == 3 && !t.has_sc && cin == 512 && mid == 128) {   // the weights never change after this (bias
+            CHK(b.chain_w.alloc((size_t)mid * cin * 2));               // calibration rewrites biases only)
+            HIPCHK(cbw_conv_chain_pack(b.conv[0].w.as<uint16_t>(), b.chain_w.as<uint16_t>(), nullptr));
+            HIPCHK(hipStreamSynchronize(nullptr));
+        }
+        h->blocks.push_back(std::move(b));
     }
     int rc;
     const auto* fw = h->ps.get("model.classifier.1.weight", (size_t)2 * h->hidden, &rc);
@@ -599,12 +621,13 @@ int build_resnet(cbw_kws* h) {
     return CBW_OK;
 }
 
-int build_projector(cbw_kws* h) {
+// the projector Linears of every layer: bf16 copies, and fp32 ones beside them when the fp32 path is built
+int build_projector(cbw_kws* h, bool f32) {
     const int L = h->cfg.n_layers, D = h->cfg.embedding_dim, U = h->cfg.proj_units;
-    h->p1.clear();
-    h->p2.clear();
-    h->p1.resize(L);
-    h->p2.resize(L);
+    for (auto* v : {&h->p1, &h->p2, &h->p1_32, &h->p2_32}) {
+        v->clear();
+        v->resize(L);
+    }
     for (int l = 0; l < L; ++l) {
         int rc;
         const std::string p = "projector." + std::to_string(l);
@@ -612,12 +635,17 @@ int build_projector(cbw_kws* h) {
         const auto* b1 = h->ps.get(p + ".0.bias", D / 2, &rc); if (!b1) return rc;
         const auto* w2 = h->ps.get(p + ".2.weight", (size_t)U * (D / 2), &rc); if (!w2) return rc;
         const auto* b2 = h->ps.get(p + ".2.bias", U, &rc); if (!b2) return rc;
-        h->p1[l].cin = D; h->p1[l].cout = D / 2; h->p1[l].relu = true;
-        h->p2[l].cin = D / 2; h->p2[l].cout = U; h->p2[l].relu = false;
-        CHK(h->p1[l].w.upload(to_bf16(*w1)));
-        CHK(h->p1[l].b.upload(*b1));
-        CHK(h->p2[l].w.upload(to_bf16(*w2)));
-        CHK(h->p2[l].b.upload(*b2));
+        auto upload = [&](const ConvShape& s, const std::vector<float>& w, const std::vector<float>& b, ConvW& c16,
+                          ConvW& c32) -> int {
+            static_cast<ConvShape&>(c16) = static_cast<ConvShape&>(c32) = s;
+            CHK(c16.w.upload(to_bf16(w)));
+            CHK(c16.b.upload(b));
+            if (f32) CHK(c32.w.upload(w));
+            if (f32) CHK(c32.b.upload(b));
+            return CBW_OK;
+        };
+        CHK(upload({D, D / 2, 1, 1, true}, *w1, *b1, h->p1[l], h->p1_32[l]));
+        CHK(upload({D / 2, U, 1, 1, false}, *w2, *b2, h->p2[l], h->p2_32[l]));
     }
     if (h->cfg.variant == 2) {
         std::vector<float> tw((size_t)L * 3 * U * U), tb((size_t)L * U);
@@ -641,97 +669,39 @@ int build_projector(cbw_kws* h) {
     return CBW_OK;
 }
 
+// the fp32 network and the compensated one; the conv modules' ReLUs: fp32 per launch (launch_conv32), compensated
+// in the record, where the last conv's is the block's ReLU after the residual sum
 int build_f32(cbw_kws* h) {
     const int L = h->cfg.n_layers;
-    std::vector<int> hs, depths;
-    bool bottleneck = true;
-    switch (h->cfg.resnet_depth) {
-        case 50: hs = {256, 512, 1024, 2048}; depths = {3, 4, 6, 3}; break;
-        case 34: hs = {64, 128, 256, 512}; depths = {3, 4, 6, 3}; bottleneck = false; break;
-        default: hs = {64, 128, 256, 512}; depths = {2, 2, 2, 2}; bottleneck = false; break;
-    }
-    const std::string root = "model.feature_extractor";
-    h->stem32.cin = L; h->stem32.cout = 64; h->stem32.k = 7; h->stem32.stride = 2; h->stem32.relu = true;
-    CHK(load_conv_bn32(h->ps, root + ".embedder.embedder", h->stem32));
+    const std::string stem = "model.feature_extractor.embedder.embedder";
+    CHK(load_conv_bn(h->ps, stem, stem_shape(L), h->stem32, true));
     if (3 * L <= 16) {   // the compensated stem (cbw_stem16_pool_x3): taps kw padded to 8, channels [hi | lo | hi | 0]
         std::vector<float> o, sh;
-        CHK(fold_conv_host(h->ps, root + ".embedder.embedder", L, 64, 7, o, sh));
+        CHK(fold_conv_host(h->ps, stem, L, 64, 7, o, sh));
         std::vector<uint16_t> w16((size_t)64 * 7 * 8 * 16, 0);
         for (int co = 0; co < 64; ++co)
             for (int kh = 0; kh < 7; ++kh)
                 for (int kw = 0; kw < 7; ++kw)
-                    for (int c = 0; c < L; ++c) {
-                        const float v = o[(((size_t)co * 7 + kh) * 7 + kw) * L + c];
-                        const uint16_t hi = f2bf_host(v);
-                        const uint32_t u = (uint32_t)hi << 16;
-                        float hv;
-                        std::memcpy(&hv, &u, 4);
-                        uint16_t* px = &w16[(((size_t)co * 7 + kh) * 8 + kw) * 16];
-                        px[c] = hi;
-                        px[L + c] = f2bf_host(v - hv);
-                        px[2 * L + c] = hi;
-                    }
+                    split3(&o[(((size_t)co * 7 + kh) * 7 + kw) * L], L, &w16[(((size_t)co * 7 + kh) * 8 + kw) * 16]);
         CHK(h->stem16x3_w.upload(w16));
     }
     h->blocks32.clear();
     h->blocks3.clear();
-    int cin = 64;
-    for (size_t s = 0; s < hs.size(); ++s) {
-        const int cout = hs[s];
-        for (int li = 0; li < depths[s]; ++li) {
-            const int stride = (li == 0 && s > 0) ? 2 : 1;
-            const std::string p = root + ".encoder.stages." + std::to_string(s) + ".layers." + std::to_string(li);
-            BlockW32 b;
-            BlockW b3;
-            if (cin != cout || stride != 1) {
-                b.has_sc = b3.has_sc = true;
-                b.sc.cin = cin; b.sc.cout = cout; b.sc.k = 1; b.sc.stride = stride;
-                CHK(load_conv_bn32(h->ps, p + ".shortcut", b.sc));
-                CHK(load_conv_bn_x3(h->ps, p + ".shortcut", cin, cout, 1, stride, false, b3.sc));
-            }
-            if (bottleneck) {
-                const int mid = cout / 4;
-                const int ci[3] = {cin, mid, mid}, co[3] = {mid, mid, cout}, k[3] = {1, 3, 1}, st[3] = {1, stride, 1};
-                b.nconv = b3.nconv = 3;
-                for (int j = 0; j < 3; ++j) {
-                    b.conv[j].cin = ci[j]; b.conv[j].cout = co[j]; b.conv[j].k = k[j]; b.conv[j].stride = st[j];
-                    CHK(load_conv_bn32(h->ps, p + ".layer." + std::to_string(j), b.conv[j]));
-                    CHK(load_conv_bn_x3(h->ps, p + ".layer." + std::to_string(j), ci[j], co[j], k[j], st[j], true,
-                                        b3.conv[j]));
-                }
-            } else {
-                b.nconv = b3.nconv = 2;
-                b.conv[0].cin = cin; b.conv[0].cout = cout; b.conv[0].k = 3; b.conv[0].stride = stride;
-                b.conv[1].cin = cout; b.conv[1].cout = cout; b.conv[1].k = 3; b.conv[1].stride = 1;
-                for (int j = 0; j < 2; ++j) CHK(load_conv_bn32(h->ps, p + ".layer." + std::to_string(j), b.conv[j]));
-                CHK(load_conv_bn_x3(h->ps, p + ".layer.0", cin, cout, 3, stride, true, b3.conv[0]));
-                CHK(load_conv_bn_x3(h->ps, p + ".layer.1", cout, cout, 3, 1, true, b3.conv[1]));
-            }
-            h->blocks32.push_back(std::move(b));
-            h->blocks3.push_back(std::move(b3));
-            cin = cout;
+    for (const BlockTopo& t : h->topo) {
+        BlockW b, b3;
+        b.nconv = b3.nconv = t.nconv;
+        b.has_sc = b3.has_sc = t.has_sc;
+        if (t.has_sc) {
+            CHK(load_conv_bn(h->ps, t.prefix + ".shortcut", t.sc, b.sc, true));
+            CHK(load_conv_bn_x3(h->ps, t.prefix + ".shortcut", t.sc, false, b3.sc));
         }
-    }
-    if (h->cfg.variant > 0) {
-        const int D = h->cfg.embedding_dim, U = h->cfg.proj_units;
-        h->p1_32.clear();
-        h->p2_32.clear();
-        h->p1_32.resize(L);
-        h->p2_32.resize(L);
-        for (int l = 0; l < L; ++l) {
-            int rc;
-            const std::string p = "projector." + std::to_string(l);
-            const auto* w1 = h->ps.get(p + ".0.weight", (size_t)(D / 2) * D, &rc); if (!w1) return rc;
-            const auto* b1 = h->ps.get(p + ".0.bias", D / 2, &rc); if (!b1) return rc;
-            const auto* w2 = h->ps.get(p + ".2.weight", (size_t)U * (D / 2), &rc); if (!w2) return rc;
-            const auto* b2 = h->ps.get(p + ".2.bias", U, &rc); if (!b2) return rc;
-            h->p1_32[l].cin = D; h->p1_32[l].cout = D / 2;
-            h->p2_32[l].cin = D / 2; h->p2_32[l].cout = U;
-            CHK(h->p1_32[l].w.upload(*w1));
-            CHK(h->p1_32[l].b.upload(*b1));
-            CHK(h->p2_32[l].w.upload(*w2));
-            CHK(h->p2_32[l].b.upload(*b2));
+        for (int j = 0; j < t.nconv; ++j) {
+            const std::string p = t.prefix + ".layer." + std::to_string(j);
+            CHK(load_conv_bn(h->ps, p, t.conv[j], b.conv[j], true));
+            CHK(load_conv_bn_x3(h->ps, p, t.conv[j], true, b3.conv[j]));
         }
+        h->blocks32.push_back(std::move(b));
+        h->blocks3.push_back(std::move(b3));
     }
     return CBW_OK;
 }
@@ -767,11 +737,12 @@ float e4m3_value_host(uint8_t c) {
 // ... with m (the conv input's per-channel means over the calibration pairs, or null) the bias also absorbs the
 // mean shift of the rounded weights, sum_{taps, c} m[c] (w - w_e4m3 alpha / s_in) -- the bf16 tier's bias
 // correction (apply_bias_correction) for the e4m3 weights
-int load_conv_f8(const ParamStore& ps, const std::string& prefix, int cin, int cout, int k, int stride, bool relu,
-                 float s_in, ConvF8& c, const double* m = nullptr) {
+int load_conv_f8(const ParamStore& ps, const std::string& prefix, const ConvShape& s, bool relu, float s_in, ConvF8& c,
+                 const double* m = nullptr) {
+    const int cin = s.cin, cout = s.cout;
     std::vector<float> o, sh;
-    CHK(fold_conv_host(ps, prefix, cin, cout, k, o, sh));
-    const size_t row = (size_t)k * k * cin;
+    CHK(fold_conv_host(ps, prefix, cin, cout, s.k, o, sh));
+    const size_t row = (size_t)s.k * s.k * cin;
     std::vector<uint8_t> q(o.size());
     std::vector<float> alpha(cout);
     for (int co = 0; co < cout; ++co) {
@@ -786,7 +757,7 @@ int load_conv_f8(const ParamStore& ps, const std::string& prefix, int cin, int c
         }
         sh[co] = (float)((double)sh[co] + corr);
     }
-    c.cin = cin; c.cout = cout; c.k = k; c.stride = stride; c.relu = relu;
+    static_cast<ConvShape&>(c) = {cin, cout, s.k, s.stride, relu};
     CHK(c.w.upload(q));
     CHK(c.alpha.upload(alpha));
     CHK(c.b.upload(sh));
@@ -794,20 +765,13 @@ int load_conv_f8(const ParamStore& ps, const std::string& prefix, int cin, int c
 }
 
 int launch_conv_f8(const cbw_kws* h, const ConvF8& c, const uint8_t* x, int N, int H, int W, void* y,
-                   const uint8_t* res, float res_scale, bool out_bf16, float y_scale, hipStream_t st, int* Ho_out,
-                   int* Wo_out, Prof* prof) {
+                   const uint8_t* res, float res_scale, bool out_bf16, float y_scale, hipStream_t st, Prof* prof) {
     F8ConvArgs a{};
     a.x = x; a.w = c.w.as<uint8_t>(); a.alpha = c.alpha.as<float>(); a.bias = c.b.as<float>();
     a.res = res; a.res_scale = res_scale; a.y = y; a.y_inv_scale = 1.f / y_scale; a.out_bf16 = out_bf16 ? 1 : 0;
     a.zero = h->zero.p;
-    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout; a.KH = a.KW = c.k;
-    a.sh = a.sw = c.stride; a.ph = a.pw = c.k / 2;
-    a.Ho = (H + 2 * a.ph - a.KH) / a.sh + 1;
-    a.Wo = (W + 2 * a.pw - a.KW) / a.sw + 1;
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, c, N, H, W);
     a.relu = c.relu ? 1 : 0;
-    if (Ho_out) *Ho_out = a.Ho;
-    if (Wo_out) *Wo_out = a.Wo;
     if (!cbw_conv_fp8_supported(a)) return fail(CBW_ERR_INVALID, "fp8 conv shape not supported");
     int slot;
     CHK(Prof::begin(prof, st, &slot));
@@ -816,33 +780,40 @@ int launch_conv_f8(const cbw_kws* h, const ConvF8& c, const uint8_t* x, int N, i
     return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel);
 }
 
-// activation sizes of one chunk through the network (elements)
+// activation sizes of one pair through the network (elements): the stem conv's output, the largest of the max-pool's
+// and the blocks' outputs (a projection shortcut's output has its block's output shape), the largest tensor inside
+// a block
+struct NetPlan {
+    size_t stem = 0, big = 0, small = 0;
+};
+
+NetPlan net_plan(const cbw_kws* h, int Tk, int Tu) {
+    NetPlan p;
+    int H = out_dim(Tk, 7, 2), W = out_dim(Tu, 7, 2);
+    p.stem = (size_t)H * W * 64;
+    H = out_dim(H, 3, 2);
+    W = out_dim(W, 3, 2);
+    p.big = (size_t)H * W * 64;
+    for (const BlockTopo& b : h->topo) {
+        const BlockDims d = block_dims(b, H, W);
+        p.small = std::max(p.small, (size_t)d.h1 * d.w1 * b.conv[0].cout);
+        if (b.nconv == 3) p.small = std::max(p.small, (size_t)d.Ho * d.Wo * b.conv[1].cout);
+        p.big = std::max(p.big, (size_t)d.Ho * d.Wo * b.conv[b.nconv - 1].cout);
+        H = d.Ho;
+        W = d.Wo;
+    }
+    return p;
+}
+
+// one chunk of the bf16 scoring pass: the stem's output shares the block buffers
 struct KwsPlan {
     size_t maps = 0, big = 0, small = 0;
 };
 
 KwsPlan kws_plan(const cbw_kws* h, int Tk, int Tu, int chunk) {
-    KwsPlan p;
+    const NetPlan q = net_plan(h, Tk, Tu);
     const size_t n = (size_t)chunk;
-    p.maps = n * Tk * Tu * stem_channels(h->cfg.n_layers);
-    int H = (Tk + 6 - 7) / 2 + 1, W = (Tu + 6 - 7) / 2 + 1;
-    p.big = n * H * W * 64;
-    H = (H + 2 - 3) / 2 + 1;
-    W = (W + 2 - 3) / 2 + 1;
-    p.big = std::max(p.big, n * H * W * 64);
-    for (const auto& b : h->blocks) {
-        int Ho = H, Wo = W;
-        for (int j = 0; j < b.nconv; ++j) {
-            const auto& c = b.conv[j];
-            Ho = (Ho + 2 * (c.k / 2) - c.k) / c.stride + 1;
-            Wo = (Wo + 2 * (c.k / 2) - c.k) / c.stride + 1;
-            const size_t e = n * Ho * Wo * c.cout;
-            if (j + 1 < b.nconv) p.small = std::max(p.small, e); else p.big = std::max(p.big, e);
-        }
-        H = Ho;
-        W = Wo;
-    }
-    return p;
+    return {n * Tk * Tu * stem_channels(h->cfg.n_layers), n * std::max(q.stem, q.big), n * q.small};
 }
 
 }  // namespace
@@ -885,9 +856,11 @@ int cbw_kws_set_param(cbw_kws* h, const char* name, const float* host, int64_t n
 
 int cbw_kws_finalize(cbw_kws* h) {
     if (!h) return fail(CBW_ERR_INVALID, "null handle");
+    const bool f32 = h->cfg.n_layers <= 4;   // the fp32 and compensated networks (the fp32 stem's input channels)
+    CHK(resnet_topology(h->cfg.resnet_depth, h->topo));
     CHK(build_resnet(h));
-    if (h->cfg.variant > 0) CHK(build_projector(h));
-    if (h->cfg.n_layers <= 4) CHK(build_f32(h));
+    if (h->cfg.variant > 0) CHK(build_projector(h, f32));
+    if (f32) CHK(build_f32(h));
     if (!h->fork_ev) {
         // only the side streams CBW_KWS_STREAMS asks for (more are created on first use, ChunkStreams::begin):
         // a process gets GPU_MAX_HW_QUEUES = 4 hardware queues, and streams beyond that share one in order
@@ -1026,8 +999,8 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
     uint16_t* SC = (uint16_t*)p; p += align_up(plan.big * 2);
     uint16_t* T1 = (uint16_t*)p; p += align_up(plan.small * 2);
     uint16_t* T2 = (uint16_t*)p;
-    const int Hs = (Tk + 6 - 7) / 2 + 1, Ws = (Tu + 6 - 7) / 2 + 1;
-    const int Hp = (Hs - 1) / 2 + 1, Wp = (Ws - 1) / 2 + 1;
+    const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
+    const int Hp = out_dim(Hs, 3, 2), Wp = out_dim(Ws, 3, 2);
     const int L = h->cfg.n_layers;
 
     // stem + max-pool of pairs [n0, n0 + nn) into X (every tensor of the chunk is [pair][H][W][C], so a pair range
@@ -1055,16 +1028,16 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
         bool t1_ready = false;   // the previous block's chained expand launch already wrote this block's T1
         for (size_t bi = b0; bi < b1; ++bi) {
             const auto& b = h->blocks[bi];
+            const BlockDims d = block_dims(h->topo[bi], H, W);
+            const int Ho = d.Ho, Wo = d.Wo;
             uint16_t* xo = at(x, H, W, C);
-            int Ho = H, Wo = W;
             const void* res = xo;
             const bool s1_first = b.nconv == 3 && b.has_sc && b.fused_sc && b.sc.stride == 1 && b.sc.cin == 64 &&
                                   b.conv[0].cin == 64 && b.conv[0].cout == 64 && b.conv[1].stride == 1 &&
                                   b.conv[2].cout == 256 && bottleneck_fusion_enabled() && bottleneck_first_enabled();
             if (b.has_sc && !b.fused_sc) {
-                const int hs = (H - 1) / b.sc.stride + 1, ws2 = (W - 1) / b.sc.stride + 1;
-                uint16_t* sco = at(SC, hs, ws2, b.sc.cout);
-                CHK(launch_conv(b.sc, xo, nn, H, W, sco, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
+                uint16_t* sco = at(SC, d.hs, d.ws, b.sc.cout);
+                CHK(launch_conv(b.sc, xo, nn, H, W, sco, nullptr, 0, h->zero.p, st, &h->prof));
                 res = sco;
             }
             if (s1_first || (b.nconv == 3 && !b.has_sc && b.conv[0].cin == 256 && b.conv[0].cout == 64 &&
@@ -1090,14 +1063,11 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
                               s1_first ? "bottleneck_kernel<64>" : "bottleneck_ring_kernel"));
             } else if (b.nconv == 3) {
                 const auto &c0 = b.conv[0], &c1 = b.conv[1], &c2 = b.conv[2];
-                const int h1 = (H + 2 * (c0.k / 2) - c0.k) / c0.stride + 1, w1 = (W + 2 * (c0.k / 2) - c0.k) / c0.stride + 1;
-                Ho = (h1 + 2 * (c1.k / 2) - c1.k) / c1.stride + 1;
-                Wo = (w1 + 2 * (c1.k / 2) - c1.k) / c1.stride + 1;
-                uint16_t* t1 = at(T1, h1, w1, c0.cout);
+                uint16_t* t1 = at(T1, d.h1, d.w1, c0.cout);
                 uint16_t* t2 = at(T2, Ho, Wo, c1.cout);
                 uint16_t* yo = at(y, Ho, Wo, c2.cout);
-                if (!t1_ready) CHK(launch_conv(c0, xo, nn, H, W, t1, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
-                CHK(launch_conv(c1, t1, nn, h1, w1, t2, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
+                if (!t1_ready) CHK(launch_conv(c0, xo, nn, H, W, t1, nullptr, 0, h->zero.p, st, &h->prof));
+                CHK(launch_conv(c1, t1, nn, d.h1, d.w1, t2, nullptr, 0, h->zero.p, st, &h->prof));
                 // identity block followed by an identity block whose reduce qualifies (ResNet-50 s2b1 -> s2b2 -> s2b3):
                 // T1 is free here (c1 above consumed it earlier on this stream) and takes the next block's reduce
                 t1_ready = false;
@@ -1109,20 +1079,16 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
                 if (t1_ready) {   // y and the next T1 are written
                 } else if (b.fused_sc) {   // y = relu([T2 | x strided] . [W_expand ; W_shortcut] + b): no shortcut tensor
                     const Src2 s2{xo, b.sc.cin, H, W, b.sc.stride};
-                    CHK(launch_conv(c2, t2, nn, Ho, Wo, yo, nullptr, CBW_EPI_RELU, h->zero.p, st, nullptr, nullptr,
-                                    &h->prof, &s2));
+                    CHK(launch_conv(c2, t2, nn, Ho, Wo, yo, nullptr, CBW_EPI_RELU, h->zero.p, st, &h->prof, &s2));
                 } else {
-                    CHK(launch_conv(c2, t2, nn, Ho, Wo, yo, res, CBW_EPI_RELU, h->zero.p, st, nullptr, nullptr,
-                                    &h->prof));
+                    CHK(launch_conv(c2, t2, nn, Ho, Wo, yo, res, CBW_EPI_RELU, h->zero.p, st, &h->prof));
                 }
             } else {
                 const auto &c0 = b.conv[0], &c1 = b.conv[1];
-                Ho = (H + 2 * (c0.k / 2) - c0.k) / c0.stride + 1;
-                Wo = (W + 2 * (c0.k / 2) - c0.k) / c0.stride + 1;
                 uint16_t* t1 = at(T1, Ho, Wo, c0.cout);
                 uint16_t* yo = at(y, Ho, Wo, c1.cout);
-                CHK(launch_conv(c0, xo, nn, H, W, t1, nullptr, 0, h->zero.p, st, nullptr, nullptr, &h->prof));
-                CHK(launch_conv(c1, t1, nn, Ho, Wo, yo, res, CBW_EPI_RELU, h->zero.p, st, nullptr, nullptr, &h->prof));
+                CHK(launch_conv(c0, xo, nn, H, W, t1, nullptr, 0, h->zero.p, st, &h->prof));
+                CHK(launch_conv(c1, t1, nn, Ho, Wo, yo, res, CBW_EPI_RELU, h->zero.p, st, &h->prof));
             }
             std::swap(x, y);
             H = Ho;
@@ -1161,23 +1127,22 @@ int resnet_chunk(cbw_kws* h, const KwsPlan& plan, char* ws, int kc, int Tk, int 
         uint8_t* sc8 = (uint8_t*)SC;
         uint8_t* t1 = (uint8_t*)T1;
         uint8_t* t2 = (uint8_t*)T2;
-        for (const BlockF8& b : h->blocks8) {
+        for (size_t i = 0; i < h->blocks8.size(); ++i) {
+            const BlockF8& b = h->blocks8[i];
+            const BlockDims d = block_dims(h->topo[h->f8_first + i], H, W);
             const uint8_t* res = cur;
             float rs = b.s_x;
             if (b.has_sc) {
-                CHK(launch_conv_f8(h, b.sc, cur, kc, H, W, sc8, nullptr, 0.f, false, b.s_sc, st, nullptr, nullptr,
-                                   &h->prof));
+                CHK(launch_conv_f8(h, b.sc, cur, kc, H, W, sc8, nullptr, 0.f, false, b.s_sc, st, &h->prof));
                 res = sc8;
                 rs = b.s_sc;
             }
-            int h1, w1, Ho, Wo;
-            CHK(launch_conv_f8(h, b.conv[0], cur, kc, H, W, t1, nullptr, 0.f, false, b.s_t1, st, &h1, &w1, &h->prof));
-            CHK(launch_conv_f8(h, b.conv[1], t1, kc, h1, w1, t2, nullptr, 0.f, false, b.s_t2, st, &Ho, &Wo, &h->prof));
-            CHK(launch_conv_f8(h, b.conv[2], t2, kc, Ho, Wo, other, res, rs, b.out_bf16, b.s_out, st, nullptr, nullptr,
-                               &h->prof));
+            CHK(launch_conv_f8(h, b.conv[0], cur, kc, H, W, t1, nullptr, 0.f, false, b.s_t1, st, &h->prof));
+            CHK(launch_conv_f8(h, b.conv[1], t1, kc, d.h1, d.w1, t2, nullptr, 0.f, false, b.s_t2, st, &h->prof));
+            CHK(launch_conv_f8(h, b.conv[2], t2, kc, d.Ho, d.Wo, other, res, rs, b.out_bf16, b.s_out, st, &h->prof));
             std::swap(cur, other);
-            H = Ho;
-            W = Wo;
+            H = d.Ho;
+            W = d.Wo;
             C = b.conv[2].cout;
         }
         HIPCHK(cbw_pool_fc((const uint16_t*)cur, h->fc_w.as<float>(), h->fc_b8.as<float>(), logits, kc, H * W, C, st));
@@ -1312,11 +1277,7 @@ int cbw_conv2d_fp8(const uint8_t* x, const uint8_t* w, const float* alpha, const
     F8ConvArgs a{};
     a.x = x; a.w = w; a.alpha = alpha; a.bias = bias; a.res = res; a.res_scale = res_scale; a.y = y;
     a.y_inv_scale = 1.f / y_scale; a.out_bf16 = out_bf16; a.zero = zp; a.relu = relu;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = a.KW = k; a.sh = a.sw = stride;
-    a.ph = a.pw = k / 2;
-    a.Ho = (H + 2 * a.ph - k) / stride + 1;
-    a.Wo = (W + 2 * a.pw - k) / stride + 1;
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, {Cin, Cout, k, stride}, N, H, W);
     if (!cbw_conv_fp8_supported(a) || y_scale <= 0.f)
         return fail(CBW_ERR_INVALID, "cbw_conv2d_fp8: 1x1 / 3x3, Cin % 128 == 0, Cout % 128 == 0, positive scales");
     HIPCHK(cbw_conv_fp8(a, (hipStream_t)stream));
@@ -1518,31 +1479,11 @@ struct ExactPlan {
     size_t maps = 0, stem = 0, big = 0, small = 0;
 };
 
+// one pass of the re-scoring tiers: the stem's output kept in its own buffer
 extern "C++" ExactPlan exact_plan(const cbw_kws* h, int Tk, int Tu, int n) {
-    ExactPlan p;
-    const int L = h->cfg.n_layers;
-    p.maps = (size_t)n * Tk * Tu * L;
-    const int Hs = (Tk + 6 - 7) / 2 + 1, Ws = (Tu + 6 - 7) / 2 + 1;
-    p.stem = (size_t)n * Hs * Ws * 64;
-    int H = (Hs - 1) / 2 + 1, W = (Ws - 1) / 2 + 1;
-    p.big = (size_t)n * H * W * 64;
-    for (const auto& b : h->blocks32) {
-        int Ho = H, Wo = W;
-        if (b.has_sc) {
-            const int hs = (H - 1) / b.sc.stride + 1, ws = (W - 1) / b.sc.stride + 1;
-            p.big = std::max(p.big, (size_t)n * hs * ws * b.sc.cout);
-        }
-        for (int j = 0; j < b.nconv; ++j) {
-            const auto& c = b.conv[j];
-            Ho = (Ho + 2 * (c.k / 2) - c.k) / c.stride + 1;
-            Wo = (Wo + 2 * (c.k / 2) - c.k) / c.stride + 1;
-            const size_t e = (size_t)n * Ho * Wo * c.cout;
-            if (j + 1 < b.nconv) p.small = std::max(p.small, e); else p.big = std::max(p.big, e);
-        }
-        H = Ho;
-        W = Wo;
-    }
-    return p;
+    const NetPlan q = net_plan(h, Tk, Tu);
+    const size_t N = (size_t)n;
+    return {N * Tk * Tu * h->cfg.n_layers, N * q.stem, N * q.big, N * q.small};
 }
 }  // namespace
 
@@ -1603,15 +1544,40 @@ struct ConvInputStats {
     std::vector<int> ch;          // channels per point (0: unused)
     std::vector<size_t> off;      // float offset of point i's [G][C] partial sums in part
     std::vector<double> rows;     // rows summed per point
-    float* part = nullptr;        // null: no channel sums
+    DevBuf part;                  // the partial sums, zeroed on st by init()
     int G = 0;
     // absolute maxima (the fp8 tier's activation scales): per block i, point 4 i + {0 input, 1 first conv's
     // output, 2 second conv's output, 3 shortcut output}; amax[p * groups + g] = workgroup g's partial
     float* amax = nullptr;
+    int init(const cbw_kws* h, hipStream_t st) {
+        G = cbw_channel_sum_groups();
+        ch = {h->cfg.n_layers};
+        for (const BlockTopo& b : h->topo)
+            ch.insert(ch.end(), {b.conv[0].cin, b.conv[0].cout, b.nconv == 3 ? b.conv[1].cout : 0});
+        size_t tot = 0;
+        for (int c : ch) { off.push_back(tot); tot += (size_t)G * c; }
+        rows.assign(ch.size(), 0.0);
+        CHK(part.alloc(tot * sizeof(float)));
+        HIPCHK(hipMemsetAsync(part.p, 0, part.bytes, st));
+        return CBW_OK;
+    }
+    // per point the channel means over the rows added (empty: nothing added); the stream's work must be complete
+    int means(std::vector<std::vector<double>>& m) const {
+        std::vector<float> host(part.bytes / sizeof(float));
+        HIPCHK(hipMemcpy(host.data(), part.p, part.bytes, hipMemcpyDeviceToHost));
+        m.assign(ch.size(), std::vector<double>());
+        for (size_t i = 0; i < ch.size(); ++i) {
+            if (!ch[i] || rows[i] <= 0) continue;
+            m[i].assign(ch[i], 0.0);
+            for (int g = 0; g < G; ++g)
+                for (int c = 0; c < ch[i]; ++c) m[i][c] += host[off[i] + (size_t)g * ch[i] + c];
+            for (double& v : m[i]) v /= rows[i];
+        }
+        return CBW_OK;
+    }
     int add(size_t i, const float* x, int64_t M, hipStream_t st) {
-        if (!part) return CBW_OK;
         rows[i] += (double)M;
-        HIPCHK(cbw_channel_sum_f32(x, M, ch[i], part + off[i], st));
+        HIPCHK(cbw_channel_sum_f32(x, M, ch[i], part.as<float>() + off[i], st));
         return CBW_OK;
     }
     int absmax(size_t p, const float* x, int64_t n, hipStream_t st) {
@@ -1664,36 +1630,33 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
         }
         HIPCHK(cbw_sim_f32(kwd, kwd_mask, utt, utt_mask, sel, c0, cn, maps, L, Tk, Tu, E, st));
         if (stats) CHK(stats->add(0, maps, (int64_t)cn * Tk * Tu, st));
-        int Hs, Ws;
-        CHK(launch_conv32(h->stem32, maps, cn, Tk, Tu, stem, nullptr, true, st, &Hs, &Ws));
-        int H = (Hs - 1) / 2 + 1, W = (Ws - 1) / 2 + 1, C = 64;
+        const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
+        CHK(launch_conv32(h->stem32, maps, cn, Tk, Tu, stem, nullptr, true, st));
+        int H = out_dim(Hs, 3, 2), W = out_dim(Ws, 3, 2), C = 64;
         HIPCHK(cbw_maxpool_f32(stem, X, cn, Hs, Ws, 64, H, W, st));
         float *x = X, *y = Y;
-        size_t bi = 0;
-        for (const auto& b : h->blocks32) {
+        for (size_t bi = 0; bi < h->blocks32.size(); ++bi) {
+            const auto& b = h->blocks32[bi];
+            const BlockDims d = block_dims(h->topo[bi], H, W);
+            const int h1 = d.h1, w1 = d.w1, Ho = d.Ho, Wo = d.Wo;
             const float* res = x;
             if (stats) CHK(stats->add(1 + 3 * bi, x, (int64_t)cn * H * W, st));
             if (stats) CHK(stats->absmax(4 * bi, x, (int64_t)cn * H * W * C, st));
             if (b.has_sc) {
                 CHK(launch_conv32(b.sc, x, cn, H, W, SC, nullptr, false, st));
                 res = SC;
-                if (stats) {
-                    const int hs = (H - 1) / b.sc.stride + 1, ws2 = (W - 1) / b.sc.stride + 1;
-                    CHK(stats->absmax(4 * bi + 3, SC, (int64_t)cn * hs * ws2 * b.sc.cout, st));
-                }
+                if (stats) CHK(stats->absmax(4 * bi + 3, SC, (int64_t)cn * d.hs * d.ws * b.sc.cout, st));
             }
-            int Ho = H, Wo = W;
             if (b.nconv == 3) {
-                int h1, w1;
-                CHK(launch_conv32(b.conv[0], x, cn, H, W, T1, nullptr, true, st, &h1, &w1));
+                CHK(launch_conv32(b.conv[0], x, cn, H, W, T1, nullptr, true, st));
                 if (stats) CHK(stats->add(2 + 3 * bi, T1, (int64_t)cn * h1 * w1, st));
                 if (stats) CHK(stats->absmax(4 * bi + 1, T1, (int64_t)cn * h1 * w1 * b.conv[0].cout, st));
-                CHK(launch_conv32(b.conv[1], T1, cn, h1, w1, T2, nullptr, true, st, &Ho, &Wo));
+                CHK(launch_conv32(b.conv[1], T1, cn, h1, w1, T2, nullptr, true, st));
                 if (stats) CHK(stats->add(3 + 3 * bi, T2, (int64_t)cn * Ho * Wo, st));
                 if (stats) CHK(stats->absmax(4 * bi + 2, T2, (int64_t)cn * Ho * Wo * b.conv[1].cout, st));
                 CHK(launch_conv32(b.conv[2], T2, cn, Ho, Wo, y, res, true, st));
             } else {
-                CHK(launch_conv32(b.conv[0], x, cn, H, W, T1, nullptr, true, st, &Ho, &Wo));
+                CHK(launch_conv32(b.conv[0], x, cn, H, W, T1, nullptr, true, st));
                 if (stats) CHK(stats->add(2 + 3 * bi, T1, (int64_t)cn * Ho * Wo, st));
                 CHK(launch_conv32(b.conv[1], T1, cn, Ho, Wo, y, res, true, st));
             }
@@ -1701,7 +1664,6 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
             H = Ho;
             W = Wo;
             C = b.conv[b.nconv - 1].cout;
-            ++bi;
         }
         if (logits)
             HIPCHK(cbw_pool_fc_f32(x, h->fc_w.as<float>(), h->fc_b.as<float>(), sel, c0, cn, logits, H * W, C, st));
@@ -1709,22 +1671,16 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
     return CBW_OK;
 }
 
-float bf16_round_host(float v) {
-    const uint32_t u = (uint32_t)f2bf_host(v) << 16;
-    float r;
-    std::memcpy(&r, &u, 4);
-    return r;
-}
-
 // the folded fp32 bias of a conv plus, with input channel means m, the bias correction
 // sum_{kh, kw, c} m[c] (w - bf16(w)): the mean shift the bf16 weights put on each output channel
-int corrected_bias(const ParamStore& ps, const std::string& prefix, int cin, int cout, int k, const double* m,
+int corrected_bias(const ParamStore& ps, const std::string& prefix, const ConvShape& shape, const double* m,
                    std::vector<double>& b) {
+    const int cin = shape.cin, cout = shape.cout;
     std::vector<float> w, sh;
-    CHK(fold_conv_host(ps, prefix, cin, cout, k, w, sh));
+    CHK(fold_conv_host(ps, prefix, cin, cout, shape.k, w, sh));
     b.assign(sh.begin(), sh.end());
     if (!m) return CBW_OK;
-    const size_t taps = (size_t)k * k;
+    const size_t taps = (size_t)shape.k * shape.k;
     for (int o = 0; o < cout; ++o) {
         double s = 0.0;
         for (size_t t = 0; t < taps; ++t) {
@@ -1751,20 +1707,20 @@ int apply_bias_correction(cbw_kws* h, const std::vector<std::vector<double>>* m)
     HIPCHK(hipDeviceSynchronize());
     auto mean = [&](size_t i) -> const double* { return m && !(*m)[i].empty() ? (*m)[i].data() : nullptr; };
     std::vector<double> b, b2;
-    CHK(corrected_bias(h->ps, "model.feature_extractor.embedder.embedder", h->cfg.n_layers, 64, 7, mean(0), b));
+    CHK(corrected_bias(h->ps, "model.feature_extractor.embedder.embedder", stem_shape(h->cfg.n_layers), mean(0), b));
     CHK(overwrite_bias(h->stem_b, b));
     for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
         BlockW& blk = h->blocks[bi];
+        const BlockTopo& t = h->topo[bi];
         const double* in[3] = {mean(1 + 3 * bi), mean(2 + 3 * bi), mean(3 + 3 * bi)};
         if (blk.has_sc && !blk.fused_sc) {
-            CHK(corrected_bias(h->ps, blk.prefix + ".shortcut", blk.sc.cin, blk.sc.cout, 1, in[0], b));
+            CHK(corrected_bias(h->ps, t.prefix + ".shortcut", t.sc, in[0], b));
             CHK(overwrite_bias(blk.sc.b, b));
         }
-        for (int j = 0; j < blk.nconv; ++j) {
-            const ConvW& c = blk.conv[j];
-            CHK(corrected_bias(h->ps, blk.prefix + ".layer." + std::to_string(j), c.cin, c.cout, c.k, in[j], b));
+        for (int j = 0; j < t.nconv; ++j) {
+            CHK(corrected_bias(h->ps, t.prefix + ".layer." + std::to_string(j), t.conv[j], in[j], b));
             if (j == 2 && blk.fused_sc) {   // + the shortcut's bias and correction (K-concatenated conv)
-                CHK(corrected_bias(h->ps, blk.prefix + ".shortcut", blk.sc.cin, blk.sc.cout, 1, in[0], b2));
+                CHK(corrected_bias(h->ps, t.prefix + ".shortcut", t.sc, in[0], b2));
                 for (size_t o = 0; o < b.size(); ++o) b[o] += b2[o];
             }
             CHK(overwrite_bias(blk.conv[j].b, b));
@@ -1810,34 +1766,12 @@ int cbw_kws_calibrate_bias(cbw_kws* h, const float* utt, const float* utt_mask, 
         return apply_bias_correction(h, nullptr);
     }
     if (!utt || !utt_mask || !kwd || !kwd_mask || !sel) return fail(CBW_ERR_INVALID, "null argument");
-    if (h->blocks.size() != h->blocks32.size()) return fail(CBW_ERR_STATE, "fp32 and bf16 networks differ");
     ConvInputStats s;
-    s.G = cbw_channel_sum_groups();
-    s.ch.push_back(h->cfg.n_layers);
-    for (const auto& b : h->blocks32) {
-        s.ch.push_back(b.conv[0].cin);
-        s.ch.push_back(b.conv[0].cout);
-        s.ch.push_back(b.nconv == 3 ? b.conv[1].cout : 0);
-    }
-    size_t tot = 0;
-    for (int c : s.ch) { s.off.push_back(tot); tot += (size_t)s.G * c; }
-    s.rows.assign(s.ch.size(), 0.0);
-    DevBuf part;
-    CHK(part.alloc(tot * sizeof(float)));
-    s.part = part.as<float>();
-    HIPCHK(hipMemsetAsync(part.p, 0, tot * sizeof(float), st));
+    CHK(s.init(h, st));
     CHK(rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, Tk, Tu, sel, n_sel, nullptr, ws, ws_bytes, st, &s));
     HIPCHK(hipStreamSynchronize(st));
-    std::vector<float> host(tot);
-    HIPCHK(hipMemcpy(host.data(), part.p, tot * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<std::vector<double>> m(s.ch.size());
-    for (size_t i = 0; i < s.ch.size(); ++i) {
-        if (!s.ch[i] || s.rows[i] <= 0) continue;
-        m[i].assign(s.ch[i], 0.0);
-        for (int g = 0; g < s.G; ++g)
-            for (int c = 0; c < s.ch[i]; ++c) m[i][c] += host[s.off[i] + (size_t)g * s.ch[i] + c];
-        for (double& v : m[i]) v /= s.rows[i];
-    }
+    std::vector<std::vector<double>> m;
+    CHK(s.means(m));
     return apply_bias_correction(h, &m);
 }
 
@@ -1846,11 +1780,10 @@ int cbw_kws_calibrate_fp8(cbw_kws* h, const float* utt, const float* utt_mask, c
                           cbw_stream_t stream) {
     if (!h || !utt || !utt_mask || !kwd || !kwd_mask || !sel || n_sel <= 0) return fail(CBW_ERR_INVALID, "null argument");
     if (!h->finalized || h->stem32.cout == 0) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no fp32 path)");
-    if (h->cfg.resnet_depth != 50 || h->blocks.size() != h->blocks32.size())
-        return fail(CBW_ERR_INVALID, "the fp8 tier covers ResNet-50 (bottleneck stages 2-4)");
+    if (h->cfg.resnet_depth != 50) return fail(CBW_ERR_INVALID, "the fp8 tier covers ResNet-50 (bottleneck stages 2-4)");
     if (!(margin > 0.f)) return fail(CBW_ERR_INVALID, "margin must be positive");
     hipStream_t st = (hipStream_t)stream;
-    const size_t nb = h->blocks32.size();
+    const size_t nb = h->topo.size();
     const char* bc = getenv("CBW_FP8_BIAS_CORR");   // 0: the folded biases (A/B)
     const bool bias_corr = !(bc && atoi(bc) == 0);
     const int G = cbw_absmax_groups();
@@ -1860,34 +1793,13 @@ int cbw_kws_calibrate_fp8(cbw_kws* h, const float* utt, const float* utt_mask, c
     ConvInputStats s;
     s.amax = amax.as<float>();
     // + the conv inputs' channel sums (the bias correction of the e4m3 weights), points as cbw_kws_calibrate_bias
-    s.G = cbw_channel_sum_groups();
-    s.ch.push_back(h->cfg.n_layers);
-    for (const auto& b : h->blocks32) {
-        s.ch.push_back(b.conv[0].cin);
-        s.ch.push_back(b.conv[0].cout);
-        s.ch.push_back(b.nconv == 3 ? b.conv[1].cout : 0);
-    }
-    size_t tot = 0;
-    for (int c : s.ch) { s.off.push_back(tot); tot += (size_t)s.G * c; }
-    s.rows.assign(s.ch.size(), 0.0);
-    DevBuf part;
-    CHK(part.alloc(tot * sizeof(float)));
-    s.part = part.as<float>();
-    HIPCHK(hipMemsetAsync(part.p, 0, tot * sizeof(float), st));
+    CHK(s.init(h, st));
     CHK(rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, Tk, Tu, sel, n_sel, nullptr, ws, ws_bytes, st, &s));
     HIPCHK(hipStreamSynchronize(st));
     std::vector<float> host(nb * 4 * G);
     HIPCHK(hipMemcpy(host.data(), amax.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<float> sums(tot);
-    HIPCHK(hipMemcpy(sums.data(), part.p, tot * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<std::vector<double>> mean(s.ch.size());
-    for (size_t i = 0; i < s.ch.size(); ++i) {
-        if (!s.ch[i] || s.rows[i] <= 0) continue;
-        mean[i].assign(s.ch[i], 0.0);
-        for (int g = 0; g < s.G; ++g)
-            for (int c = 0; c < s.ch[i]; ++c) mean[i][c] += sums[s.off[i] + (size_t)g * s.ch[i] + c];
-        for (double& v : mean[i]) v /= s.rows[i];
-    }
+    std::vector<std::vector<double>> mean;
+    CHK(s.means(mean));
     auto mp = [&](size_t i) -> const double* { return bias_corr && !mean[i].empty() ? mean[i].data() : nullptr; };
     auto scale = [&](size_t p) {
         float m = 0.f;
@@ -1896,27 +1808,24 @@ int cbw_kws_calibrate_fp8(cbw_kws* h, const float* utt, const float* utt_mask, c
     };
     int first = -1;
     for (size_t i = 0; i < nb; ++i)
-        if (h->blocks[i].stage >= 2) { first = (int)i; break; }
+        if (h->topo[i].stage >= 2) { first = (int)i; break; }
     if (first < 0) return fail(CBW_ERR_STATE, "no stage-2 blocks");
     std::vector<BlockF8> b8(nb - first);
     for (size_t i = first; i < nb; ++i) {
-        const BlockW32& b = h->blocks32[i];
+        const BlockTopo& b = h->topo[i];
         BlockF8& q = b8[i - first];
         if (b.nconv != 3) return fail(CBW_ERR_INVALID, "bottleneck blocks only");
-        const std::string& p = h->blocks[i].prefix;
+        const std::string& p = b.prefix;
         q.s_x = scale(4 * i); q.s_t1 = scale(4 * i + 1); q.s_t2 = scale(4 * i + 2);
         q.has_sc = b.has_sc;
         if (b.has_sc) {
             q.s_sc = scale(4 * i + 3);
-            CHK(load_conv_f8(h->ps, p + ".shortcut", b.sc.cin, b.sc.cout, 1, b.sc.stride, false, q.s_x, q.sc,
-                             mp(1 + 3 * i)));
+            CHK(load_conv_f8(h->ps, p + ".shortcut", b.sc, false, q.s_x, q.sc, mp(1 + 3 * i)));
         }
-        CHK(load_conv_f8(h->ps, p + ".layer.0", b.conv[0].cin, b.conv[0].cout, 1, 1, true, q.s_x, q.conv[0],
-                         mp(1 + 3 * i)));
-        CHK(load_conv_f8(h->ps, p + ".layer.1", b.conv[1].cin, b.conv[1].cout, 3, b.conv[1].stride, true, q.s_t1,
-                         q.conv[1], mp(2 + 3 * i)));
-        CHK(load_conv_f8(h->ps, p + ".layer.2", b.conv[2].cin, b.conv[2].cout, 1, 1, true, q.s_t2, q.conv[2],
-                         mp(3 + 3 * i)));
+        const float s_in[3] = {q.s_x, q.s_t1, q.s_t2};   // each conv's input scale; the third's ReLU follows the sum
+        for (int j = 0; j < 3; ++j)
+            CHK(load_conv_f8(h->ps, p + ".layer." + std::to_string(j), b.conv[j], true, s_in[j], q.conv[j],
+                             mp(1 + j + 3 * i)));
         q.out_bf16 = i + 1 == nb;
         q.s_out = q.out_bf16 ? 1.f : scale(4 * (i + 1));
     }
@@ -1982,45 +1891,44 @@ int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, cons
         // [hi | hi | lo] channels of an NHWC16 image, cbw_stem16_pool_x3; CBW_X3_STEM32=1 or 3 L > 16: the fp32
         // stem, max-pool and split)
         HIPCHK(cbw_sim_f32(kwd, kwd_mask, utt, utt_mask, sel, c0, cn, maps, L, Tk, Tu, E, st));
-        const int Hs = (Tk + 2 * 3 - 7) / 2 + 1, Ws = (Tu + 2 * 3 - 7) / 2 + 1;
-        int H = (Hs - 1) / 2 + 1, W = (Ws - 1) / 2 + 1, C = 64;
+        const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
+        int H = out_dim(Hs, 3, 2), W = out_dim(Ws, 3, 2), C = 64;
         if (h->stem16x3_w.p && !x3_stem32()) {
             uint16_t* m16 = (uint16_t*)stem;   // [cn][Tk][Tu][16] bf16 fits the fp32 stem buffer
             HIPCHK(cbw_maps_split16(maps, m16, cn, L, Tk, Tu, st));
             HIPCHK(cbw_stem16_pool_x3(m16, h->stem16x3_w.as<uint16_t>(), h->stem32.b.as<float>(), X3, cn, Tk, Tu, Hs,
                                       Ws, H, W, st));
         } else {
-            int hs2, ws2;
-            CHK(launch_conv32(h->stem32, maps, cn, Tk, Tu, stem, nullptr, true, st, &hs2, &ws2));
+            CHK(launch_conv32(h->stem32, maps, cn, Tk, Tu, stem, nullptr, true, st));
             HIPCHK(cbw_maxpool_f32(stem, X32, cn, Hs, Ws, 64, H, W, st));
             HIPCHK(cbw_split3(X32, X3, (int64_t)cn * H * W, 64, st));
         }
         uint16_t *x3 = X3, *y3 = Y3;
         for (size_t bi = 0; bi < nb; ++bi) {
             const auto& b = h->blocks3[bi];
+            const BlockDims d = block_dims(h->topo[bi], H, W);
+            const int Ho = d.Ho, Wo = d.Wo;
             const void* res = x3;   // identity shortcut: the block input's [hi | lo]
             bool res_split = true;
             if (b.has_sc) {
-                CHK(launch_conv_x3(b.sc, x3, cn, H, W, SC32, nullptr, nullptr, false, CBW_EPI_OUT_F32, zp, st, nullptr,
-                                   nullptr, &h->prof));
+                CHK(launch_conv_x3(b.sc, x3, cn, H, W, SC32, nullptr, nullptr, false, CBW_EPI_OUT_F32, zp, st,
+                                   &h->prof));
                 res = SC32;
                 res_split = false;
             }
             float* out32 = bi + 1 == nb ? X32 : nullptr;   // fp32 network output for the pool + classifier
-            int Ho = H, Wo = W;
             if (b.nconv == 3) {
-                int h1, w1;
-                CHK(launch_conv_x3(b.conv[0], x3, cn, H, W, T1, nullptr, nullptr, false, CBW_EPI_SPLIT3, zp, st, &h1,
-                                   &w1, &h->prof));
-                CHK(launch_conv_x3(b.conv[1], T1, cn, h1, w1, T2, nullptr, nullptr, false, CBW_EPI_SPLIT3, zp, st, &Ho,
-                                   &Wo, &h->prof));
-                CHK(launch_conv_x3(b.conv[2], T2, cn, Ho, Wo, y3, out32, res, res_split, CBW_EPI_SPLIT3, zp, st, nullptr,
-                                   nullptr, &h->prof));
+                CHK(launch_conv_x3(b.conv[0], x3, cn, H, W, T1, nullptr, nullptr, false, CBW_EPI_SPLIT3, zp, st,
+                                   &h->prof));
+                CHK(launch_conv_x3(b.conv[1], T1, cn, d.h1, d.w1, T2, nullptr, nullptr, false, CBW_EPI_SPLIT3, zp, st,
+                                   &h->prof));
+                CHK(launch_conv_x3(b.conv[2], T2, cn, Ho, Wo, y3, out32, res, res_split, CBW_EPI_SPLIT3, zp, st,
+                                   &h->prof));
             } else {
-                CHK(launch_conv_x3(b.conv[0], x3, cn, H, W, T1, nullptr, nullptr, false, CBW_EPI_SPLIT3, zp, st, &Ho,
-                                   &Wo, &h->prof));
-                CHK(launch_conv_x3(b.conv[1], T1, cn, Ho, Wo, y3, out32, res, res_split, CBW_EPI_SPLIT3, zp, st, nullptr,
-                                   nullptr, &h->prof));
+                CHK(launch_conv_x3(b.conv[0], x3, cn, H, W, T1, nullptr, nullptr, false, CBW_EPI_SPLIT3, zp, st,
+                                   &h->prof));
+                CHK(launch_conv_x3(b.conv[1], T1, cn, Ho, Wo, y3, out32, res, res_split, CBW_EPI_SPLIT3, zp, st,
+                                   &h->prof));
             }
             std::swap(x3, y3);
             H = Ho;
@@ -2340,11 +2248,11 @@ int cbw_encoder_hs(cbw_encoder* h, const uint16_t* mel, int B, const int32_t* la
         CHK(launch_conv(L.qkv, a, 1, 1, M, qkv, nullptr, 0, h->zero.p, st));
         HIPCHK(cbw_attention(qkv, att, B, T, H, 64, st));
         CHK(launch_conv(L.out, att, 1, 1, M, hbuf, hbuf, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st, nullptr,
-                        nullptr, nullptr, nullptr, part));
+                        nullptr, part));
         HIPCHK(cbw_layernorm(hbuf, L.ln2_g.as<float>(), L.ln2_b.as<float>(), a, nullptr, M, D, 1e-5f, st));
         CHK(launch_conv(L.fc1, a, 1, 1, M, f, nullptr, CBW_EPI_GELU, h->zero.p, st));
         CHK(launch_conv(L.fc2, f, 1, 1, M, hbuf, hbuf, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st, nullptr,
-                        nullptr, nullptr, nullptr, part));
+                        nullptr, part));
         if (i + 1 < N) CHK(capture(i + 1));
     }
     if (last_layer >= N) {
