@@ -165,6 +165,43 @@ class KwsEngine:
                        f"cbw_kws_rescore ({tier})")
         return logits
 
+    def rescore_pairs(self, utt32: torch.Tensor, utt_mask: torch.Tensor, kwd32: torch.Tensor, kwd_mask: torch.Tensor,
+                      pair_utt, pair_kwd, logits: torch.Tensor, sel, trusted: bool = False,
+                      tier: str = "fp32") -> torch.Tensor:
+        """The pairs form of ``rescore`` (cbw_kws_rescore_pairs / cbw_kws_rescore_x3_pairs): utt32 f32 [B, L, Tu, E],
+        utt_mask f32 [B, L, Tu], kwd32 f32 [K, L, Tk, E] from project_f32; pair p = (pair_utt[p], pair_kwd[p]) as
+        ``score_pairs`` takes them, or both None for every utterance against every keyword (p = b * K + k).  ``sel``
+        indexes the P pairs, which are the rows of ``logits`` (contiguous f32, 2 P elements: [P, 2] or [B, K, 2]);
+        the selected rows are rewritten in place with the tier's logits, bit-identical to what ``rescore`` gives for
+        that utterance and keyword alone.  The index ranges are checked before any launch unless ``trusted``."""
+        utt32, utt_mask, kwd32, kwd_mask = self._check_batch(utt32, utt_mask, kwd32, kwd_mask, dtype=torch.float32)
+        if tier not in ("fp32", "x3"):
+            raise ValueError(f"unknown re-scoring tier {tier}")
+        K, _, Tk, _ = kwd32.shape
+        B, _, Tu, _ = utt32.shape
+        pu, pk, P = self._pair_list(pair_utt, pair_kwd, B, K, trusted)
+        sel = self._pair_index(sel, P, trusted, "sel")
+        n = sel.numel()
+        if n == 0:
+            return logits
+        if n > P:
+            raise ValueError(f"sel has {n} entries for {P} pairs")
+        if (logits.numel() != 2 * P or logits.shape[-1] != 2 or logits.dtype != torch.float32
+                or not logits.is_contiguous() or logits.device != self.device):
+            raise ValueError(f"rescore_pairs: logits must be contiguous f32 on {self.device} with one row of 2 per pair "
+                             f"({P} pairs), got {tuple(logits.shape)} {logits.dtype}")
+        wsq, call = ((self.lib.cbw_kws_rescore_workspace_bytes, self.lib.cbw_kws_rescore_pairs) if tier == "fp32" else
+                     (self.lib.cbw_kws_rescore_x3_workspace_bytes, self.lib.cbw_kws_rescore_x3_pairs))
+        with torch.cuda.device(self.device):
+            nb = wsq(self.h, Tk, Tu)
+            if nb < 0:
+                _lib.check(-4, f"cbw_kws_rescore_pairs ({tier}) workspace")
+            ws = self._ws_rescore.get(nb, self.device)
+            _lib.check(call(self.h, utt32.data_ptr(), utt_mask.data_ptr(), B, kwd32.data_ptr(), kwd_mask.data_ptr(), K,
+                            Tk, Tu, _lib.ptr(pu), _lib.ptr(pk), P, sel.data_ptr(), n, logits.data_ptr(), ws.data_ptr(),
+                            ws.numel(), _lib.stream_handle()), f"cbw_kws_rescore_pairs ({tier})")
+        return logits
+
     def calibrate_bias(self, utt32: Optional[torch.Tensor] = None, utt_mask: Optional[torch.Tensor] = None,
                        kwd32: Optional[torch.Tensor] = None, kwd_mask: Optional[torch.Tensor] = None,
                        sel: Optional[torch.Tensor] = None, utt: Optional[torch.Tensor] = None,
@@ -407,8 +444,9 @@ class KwsEngine:
             raise ValueError(f"logits_out must be contiguous f32 {list(shape)}, got {tuple(logits_out.shape)}")
         return logits_out
 
-    def _check_batch(self, utt, utt_mask, kwd, kwd_mask):
-        """Shape / dtype checks of ``score`` for a batch of utterances: utt bf16 [B, L, Tu, E]."""
+    def _check_batch(self, utt, utt_mask, kwd, kwd_mask, dtype=torch.bfloat16):
+        """Shape / dtype checks of ``score`` for a batch of utterances: utt bf16 [B, L, Tu, E]; with ``dtype``
+        torch.float32 the same checks on the fp32 projections the re-scoring tiers take."""
         if utt.dim() != 4 or kwd.dim() != 4:
             raise ValueError(f"expected utt [B, L, Tu, E] and kwd [K, L, Tk, E], got {tuple(utt.shape)} "
                              f"{tuple(kwd.shape)}")
@@ -416,8 +454,9 @@ class KwsEngine:
         B, _, Tu, _ = utt.shape
         if B < 1 or L != self.n_layers or E != self.feat_dim or tuple(utt.shape) != (B, L, Tu, E):
             raise ValueError(f"shape mismatch: kwd {tuple(kwd.shape)} utt {tuple(utt.shape)}")
-        if utt.dtype != torch.bfloat16 or kwd.dtype != torch.bfloat16:
-            raise ValueError("projected features must be bf16 (use KwsEngine.project)")
+        if utt.dtype != dtype or kwd.dtype != dtype:
+            raise ValueError("projected features must be bf16 (use KwsEngine.project)" if dtype == torch.bfloat16 else
+                             "the re-scoring tiers take the fp32 projections (KwsEngine.project_f32)")
         if tuple(kwd_mask.shape) != (K, L, Tk) or tuple(utt_mask.shape) != (B, L, Tu):
             raise ValueError(f"mask shapes {tuple(kwd_mask.shape)} {tuple(utt_mask.shape)} for kwd {tuple(kwd.shape)} "
                              f"utt {tuple(utt.shape)}")
@@ -481,6 +520,90 @@ class KwsEngine:
         logits = self._logits(logits_out, (B, K, 2))
         self._call_score_pairs(utt, utt_mask, kwd, kwd_mask, None, None, B * K, logits, None, chunk)
         return logits
+
+    def _pair_list(self, pair_utt, pair_kwd, B: int, K: int, trusted: bool):
+        """(pair_utt, pair_kwd, P) as device int32 tensors through ``_pair_index``, or (None, None, B * K) for both
+        None: every utterance against every keyword, pair p = b * K + k."""
+        if pair_utt is None and pair_kwd is None:
+            return None, None, B * K
+        if pair_utt is None or pair_kwd is None:
+            raise ValueError("pair_utt and pair_kwd must both be given or both be None")
+        pu = self._pair_index(pair_utt, B, trusted, "pair_utt")
+        pk = self._pair_index(pair_kwd, K, trusted, "pair_kwd")
+        if pk.numel() != pu.numel():
+            raise ValueError(f"pair_utt has {pu.numel()} entries, pair_kwd {pk.numel()}")
+        if pu.numel() > 0 and K < 1:
+            raise ValueError("pairs given but no keywords")
+        return pu, pk, pu.numel()
+
+    def score_pairs_exact(self, utt: torch.Tensor, utt_mask: torch.Tensor, kwd: torch.Tensor, kwd_mask: torch.Tensor,
+                          utt32: torch.Tensor, kwd32: torch.Tensor, pair_utt, pair_kwd, threshold: float, band: float,
+                          ghost: Optional[torch.Tensor] = None, chunk: Optional[int] = None,
+                          logits_out: Optional[torch.Tensor] = None, band_x3: Optional[float] = None,
+                          band_scaled: bool = False, trusted: bool = False, features: bool = False):
+        """``score_exact`` for a pair list: every pair scored in bf16 in one pass (``score_pairs``), one band
+        selection over the P rows (cbw_kws_band), then the selected pairs re-scored from the fp32 projections
+        ``utt32`` [B, L, Tu, E] / ``kwd32`` [K, L, Tk, E] by ``rescore_pairs`` -- in fp32, or with ``band_x3`` on the
+        compensated tier and then those still within ``band_x3`` in fp32, sequenced as ``score_exact`` does.  One
+        host read-back per band selection and one re-scoring call per tier for the whole list, where P
+        ``score_exact`` calls pay both per utterance.  pair_utt / pair_kwd as ``score_pairs``, or both None for the
+        cross product p = b * K + k.  ``ghost`` is the per-keyword mask f32 [K] of ``score_exact``, gathered to pair
+        order on the device.  The fp8 first tier stays per utterance (``score_exact``'s ``fp8_band``); it has no
+        pairs form.
+
+        Returns (logits f32 [P, 2], stats) with ``score_exact``'s stats keys (+ the bf16 pass's features f32
+        [P, L, Tk, Tu] as a third element with ``features``)."""
+        utt, utt_mask, kwd, kwd_mask = self._check_batch(utt, utt_mask, kwd, kwd_mask)
+        K, L, Tk, _ = kwd.shape
+        B, _, Tu, _ = utt.shape
+        pu, pk, P = self._pair_list(pair_utt, pair_kwd, B, K, trusted)
+        logits = self._logits(logits_out, (P, 2))
+        feats = torch.empty((P, L, Tk, Tu), dtype=torch.float32, device=self.device) if features else None
+        self._call_score_pairs(utt, utt_mask, kwd, kwd_mask, pu, pk, P, logits, feats, chunk)
+        stats = {"band": 0, "fp32": 0, "bf16": P}
+
+        def done():
+            return (logits, stats, feats) if features else (logits, stats)
+        if band <= 0 or P == 0:
+            return done()
+        g = None
+        if ghost is not None:
+            g = ghost.to(self.device, torch.float32).reshape(-1)
+            if g.numel() != K:
+                raise ValueError(f"ghost mask of {g.numel()} entries for {K} keywords")
+            g = g.repeat(B) if pk is None else g[pk.long()]
+        sel, n = self.band(logits, threshold, band, g, scaled=band_scaled)
+        stats["band"] = n
+        if n == 0:
+            return done()
+        if band_x3 is None:
+            self.rescore_pairs(utt32, utt_mask, kwd32, kwd_mask, pu, pk, logits, sel, trusted=True)
+            stats["fp32"] = n
+            return done()
+        self.rescore_pairs(utt32, utt_mask, kwd32, kwd_mask, pu, pk, logits, sel, trusted=True, tier="x3")
+        sel2, n2 = self.band(logits, threshold, band_x3, g)
+        if n2:
+            self.rescore_pairs(utt32, utt_mask, kwd32, kwd_mask, pu, pk, logits, sel2, trusted=True)
+        stats["fp32"] = n2
+        return done()
+
+    def score_batch_exact(self, utt: torch.Tensor, utt_mask: torch.Tensor, kwd: torch.Tensor, kwd_mask: torch.Tensor,
+                          utt32: torch.Tensor, kwd32: torch.Tensor, threshold: float, band: float,
+                          ghost: Optional[torch.Tensor] = None, chunk: Optional[int] = None,
+                          logits_out: Optional[torch.Tensor] = None, band_x3: Optional[float] = None,
+                          band_scaled: bool = False):
+        """``score_exact`` for every utterance of a batch against every keyword: ``score_pairs_exact`` over the cross
+        product without index arrays, the per-keyword ``ghost`` tiled over the B utterances -- one band selection
+        and one re-scoring call per tier for the whole batch.  Returns (logits f32 [B, K, 2], stats): row b is what
+        ``score_exact`` gives for utterance b, the stats are the sums over b.  No fp8 first tier (per utterance
+        only)."""
+        utt, utt_mask, kwd, kwd_mask = self._check_batch(utt, utt_mask, kwd, kwd_mask)
+        B, K = utt.shape[0], kwd.shape[0]
+        out = self._logits(logits_out, (B, K, 2))
+        _, stats = self.score_pairs_exact(utt, utt_mask, kwd, kwd_mask, utt32, kwd32, None, None, threshold, band,
+                                          ghost=ghost, chunk=chunk, logits_out=out.view(B * K, 2), band_x3=band_x3,
+                                          band_scaled=band_scaled, trusted=True)
+        return out, stats
 
     def classify(self, maps: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
         """Resnet.forward (resnet.py:51-58) on NCHW f32 maps [K, L, H, W] -> logits [K, 2]."""

@@ -240,6 +240,12 @@ struct F32ConvArgs {
 hipError_t cbw_conv_f32(const F32ConvArgs& a, hipStream_t st);   // Cout % 64 == 0
 hipError_t cbw_sim_f32(const float* kwd, const float* kwd_mask, const float* utt, const float* utt_mask, const int* sel,
                        int p0, int P, float* out, int L, int Tk, int Tu, int E, hipStream_t st);
+// the same maps for P pairs of a pair list: utt f32 [B][L][Tu][E], utt_mask f32 [B][L][Tu]; map p = pair
+// sel[p0 + p] of the n_pairs pairs = (pair_utt[q], pair_kwd[q]) (device int32 [n_pairs]), or with both null
+// q = b * K + k.  q, b and k are clamped into range in the kernel.
+hipError_t cbw_sim_f32_pairs(const float* kwd, const float* kwd_mask, int K, const float* utt, const float* utt_mask,
+                             int B, const int32_t* pair_utt, const int32_t* pair_kwd, int n_pairs, const int* sel, int p0,
+                             int P, float* out, int L, int Tk, int Tu, int E, hipStream_t st);
 hipError_t cbw_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, hipStream_t st);
 hipError_t cbw_pool_fc_f32(const float* x, const float* w, const float* b, const int* sel, int p0, int P, float* logits,
                            int HW, int C, hipStream_t st);

@@ -147,17 +147,19 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(F32ConvArgs a) {
         }
 }
 
-// maps NHWC f32 [P][Tk][Tu][L]: pair p = keyword sel[p0 + p]; block (p, i) = one keyword frame
-__global__ __launch_bounds__(256) void sim_f32_kernel(const float* __restrict__ kwd, const float* __restrict__ kwd_mask,
-                                                      const float* __restrict__ utt, const float* __restrict__ utt_mask,
-                                                      const int* __restrict__ sel, int p0, float* __restrict__ out,
-                                                      int L, int Tk, int Tu, int E) {
-    extern __shared__ float kr[];   // [L][E]
-    const int p = blockIdx.y, i = blockIdx.x;
-    const int k = sel[p0 + p];
+// The fp32 similarity maps, NHWC f32 [P][Tk][Tu][L].  The two bodies below compute one map from the base pointers
+// of its own operands: kwd f32 [L][Tk][E], kwd_mask f32 [L][Tk], utt f32 [L][Tu][E], utt_mask f32 [L][Tu], out
+// f32 [Tk][Tu][L].  The __global__ wrappers after them choose the operands: the per-utterance kernels take keyword
+// sel[p0 + p] against the one utterance, the pair kernels resolve sel[p0 + p] to an (utterance, keyword) pair.  Both
+// run the same body on the same values, so a pair's map equals the per-utterance kernel's bit for bit.
+
+// generic E: block i = one keyword frame, its [L][E] rows in LDS
+CBW_DEV void sim_f32_body(const float* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                          const float* __restrict__ utt, const float* __restrict__ utt_mask, float* __restrict__ out,
+                          float* kr, int i, int L, int Tk, int Tu, int E) {
     for (int e = threadIdx.x; e < L * E; e += 256) {
         const int l = e / E;
-        kr[e] = kwd[(((int64_t)k * L + l) * Tk + i) * E + (e - l * E)];
+        kr[e] = kwd[((int64_t)l * Tk + i) * E + (e - l * E)];
     }
     __syncthreads();
     for (int j = threadIdx.x; j < Tu; j += 256) {
@@ -172,27 +174,22 @@ __global__ __launch_bounds__(256) void sim_f32_kernel(const float* __restrict__ 
                 s = fmaf(q[e + 2], uv[2], s);
                 s = fmaf(q[e + 3], uv[3], s);
             }
-            s = s * kwd_mask[((int64_t)k * L + l) * Tk + i] * utt_mask[(int64_t)l * Tu + j];
-            out[(((int64_t)p * Tk + i) * Tu + j) * L + l] = s;
+            s = s * kwd_mask[(int64_t)l * Tk + i] * utt_mask[(int64_t)l * Tu + j];
+            out[((int64_t)i * Tu + j) * L + l] = s;
         }
     }
 }
 
-// E = 64 fast path: one block per (keyword pair, 256 utterance frames); the keyword's [L][Tk][64] rows sit
-// in LDS, each thread keeps its utterance frame's 64 floats of one layer in registers and runs the Tk dot
-// products against broadcast LDS reads (the utterance is read once per block, not once per keyword frame)
-__global__ __launch_bounds__(256) void sim_f32_e64_kernel(const float* __restrict__ kwd, const float* __restrict__ kwd_mask,
-                                                          const float* __restrict__ utt, const float* __restrict__ utt_mask,
-                                                          const int* __restrict__ sel, int p0, float* __restrict__ out,
-                                                          int L, int Tk, int Tu) {
-    extern __shared__ float kr[];   // [L][Tk][64], then the keyword mask [L][Tk]
-    const int p = blockIdx.y;
-    const int k = sel[p0 + p];
+// E = 64 fast path: one block per (map, 256 utterance frames); the keyword's [L][Tk][64] rows sit in LDS, each
+// thread keeps its utterance frame's 64 floats of one layer in registers and runs the Tk dot products against
+// broadcast LDS reads (the utterance is read once per block, not once per keyword frame)
+CBW_DEV void sim_f32_e64_body(const float* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                              const float* __restrict__ utt, const float* __restrict__ utt_mask,
+                              float* __restrict__ out, float* kr, int L, int Tk, int Tu) {
     const int n = L * Tk * 64;
-    const float* ksrc = kwd + (int64_t)k * n;
-    for (int e = threadIdx.x * 4; e < n; e += 256 * 4) *(f32x4*)(kr + e) = *(const f32x4*)(ksrc + e);
+    for (int e = threadIdx.x * 4; e < n; e += 256 * 4) *(f32x4*)(kr + e) = *(const f32x4*)(kwd + e);
     float* km = kr + n;
-    for (int e = threadIdx.x; e < L * Tk; e += 256) km[e] = kwd_mask[(int64_t)k * L * Tk + e];
+    for (int e = threadIdx.x; e < L * Tk; e += 256) km[e] = kwd_mask[e];
     __syncthreads();
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= Tu) return;
@@ -213,9 +210,86 @@ __global__ __launch_bounds__(256) void sim_f32_e64_kernel(const float* __restric
                 s = fmaf(kv[2], u[c][2], s);
                 s = fmaf(kv[3], u[c][3], s);
             }
-            out[(((int64_t)p * Tk + i) * Tu + j) * L + l] = s * km[l * Tk + i] * um;
+            out[((int64_t)i * Tu + j) * L + l] = s * km[l * Tk + i] * um;
         }
     }
+}
+
+// one utterance (cbw_sim_f32): map p of the pass = keyword sel[p0 + p]; grid (Tk, P)
+__global__ __launch_bounds__(256) void sim_f32_kernel(const float* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                                                      const float* __restrict__ utt, const float* __restrict__ utt_mask,
+                                                      const int* __restrict__ sel, int p0, float* __restrict__ out,
+                                                      int L, int Tk, int Tu, int E) {
+    extern __shared__ float kr[];   // [L][E]
+    const int p = blockIdx.y;
+    const int k = sel[p0 + p];
+    sim_f32_body(kwd + (int64_t)k * L * Tk * E, kwd_mask + (int64_t)k * L * Tk, utt, utt_mask,
+                 out + (int64_t)p * Tk * Tu * L, kr, blockIdx.x, L, Tk, Tu, E);
+}
+
+// grid ((Tu + 255) / 256, P)
+__global__ __launch_bounds__(256) void sim_f32_e64_kernel(const float* __restrict__ kwd, const float* __restrict__ kwd_mask,
+                                                          const float* __restrict__ utt, const float* __restrict__ utt_mask,
+                                                          const int* __restrict__ sel, int p0, float* __restrict__ out,
+                                                          int L, int Tk, int Tu) {
+    extern __shared__ float kr[];   // [L][Tk][64], then the keyword mask [L][Tk]
+    const int p = blockIdx.y;
+    const int k = sel[p0 + p];
+    sim_f32_e64_body(kwd + (int64_t)k * L * Tk * 64, kwd_mask + (int64_t)k * L * Tk, utt, utt_mask,
+                     out + (int64_t)p * Tk * Tu * L, kr, L, Tk, Tu);
+}
+
+// A pair list (cbw_sim_f32_pairs): utt f32 [B][L][Tu][E] and utt_mask f32 [B][L][Tu] hold B utterances, and map p
+// of the pass is pair q = sel[p0 + p] of the n_pairs pairs: (utterance pair_utt[q], keyword pair_kwd[q]), or with
+// both index arrays null the cross product q = b * K + k.  q, b and k are clamped into range before any address
+// is formed, so a bad index gives a wrong map, never an out-of-range read (as kws_kernels.hip's pair_indices).
+CBW_DEV void pair_of_sel(const int* __restrict__ sel, int i, const int32_t* __restrict__ pair_utt,
+                         const int32_t* __restrict__ pair_kwd, int n_pairs, int B, int K, int& b, int& k) {
+    const int q = min(max(sel[i], 0), n_pairs - 1);
+    if (pair_utt) {
+        b = pair_utt[q];
+        k = pair_kwd[q];
+    } else {
+        b = q / K;
+        k = q - b * K;
+    }
+    b = min(max(b, 0), B - 1);
+    k = min(max(k, 0), K - 1);
+}
+
+// grid (Tk, P), as sim_f32_kernel
+__global__ __launch_bounds__(256) void sim_f32_pairs_kernel(const float* __restrict__ kwd,
+                                                            const float* __restrict__ kwd_mask,
+                                                            const float* __restrict__ utt,
+                                                            const float* __restrict__ utt_mask,
+                                                            const int32_t* __restrict__ pair_utt,
+                                                            const int32_t* __restrict__ pair_kwd, int n_pairs,
+                                                            const int* __restrict__ sel, int p0, float* __restrict__ out,
+                                                            int B, int K, int L, int Tk, int Tu, int E) {
+    extern __shared__ float kr[];   // [L][E]
+    const int p = blockIdx.y;
+    int b, k;
+    pair_of_sel(sel, p0 + p, pair_utt, pair_kwd, n_pairs, B, K, b, k);
+    sim_f32_body(kwd + (int64_t)k * L * Tk * E, kwd_mask + (int64_t)k * L * Tk, utt + (int64_t)b * L * Tu * E,
+                 utt_mask + (int64_t)b * L * Tu, out + (int64_t)p * Tk * Tu * L, kr, blockIdx.x, L, Tk, Tu, E);
+}
+
+// grid ((Tu + 255) / 256, P), as sim_f32_e64_kernel
+__global__ __launch_bounds__(256) void sim_f32_e64_pairs_kernel(const float* __restrict__ kwd,
+                                                                const float* __restrict__ kwd_mask,
+                                                                const float* __restrict__ utt,
+                                                                const float* __restrict__ utt_mask,
+                                                                const int32_t* __restrict__ pair_utt,
+                                                                const int32_t* __restrict__ pair_kwd, int n_pairs,
+                                                                const int* __restrict__ sel, int p0,
+                                                                float* __restrict__ out, int B, int K, int L, int Tk,
+                                                                int Tu) {
+    extern __shared__ float kr[];   // [L][Tk][64], then the keyword mask [L][Tk]
+    const int p = blockIdx.y;
+    int b, k;
+    pair_of_sel(sel, p0 + p, pair_utt, pair_kwd, n_pairs, B, K, b, k);
+    sim_f32_e64_body(kwd + (int64_t)k * L * Tk * 64, kwd_mask + (int64_t)k * L * Tk, utt + (int64_t)b * L * Tu * 64,
+                     utt_mask + (int64_t)b * L * Tu, out + (int64_t)p * Tk * Tu * L, kr, L, Tk, Tu);
 }
 
 __global__ void maxpool_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C,
@@ -369,6 +443,22 @@ hipError_t cbw_sim_f32(const float* kwd, const float* kwd_mask, const float* utt
     }
     hipLaunchKernelGGL(sim_f32_kernel, dim3(Tk, P), dim3(256), (size_t)L * E * 4, st, kwd, kwd_mask, utt, utt_mask, sel,
                        p0, out, L, Tk, Tu, E);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sim_f32_pairs(const float* kwd, const float* kwd_mask, int K, const float* utt, const float* utt_mask,
+                             int B, const int32_t* pair_utt, const int32_t* pair_kwd, int n_pairs, const int* sel, int p0,
+                             int P, float* out, int L, int Tk, int Tu, int E, hipStream_t st) {
+    if (E % 4 || P <= 0 || B < 1 || K < 1 || n_pairs < 1 || p0 < 0 || (pair_utt == nullptr) != (pair_kwd == nullptr))
+        return hipErrorInvalidValue;
+    const size_t lds64 = (size_t)L * Tk * (64 + 1) * 4;
+    if (E == 64 && lds64 <= 128 * 1024) {
+        hipLaunchKernelGGL(sim_f32_e64_pairs_kernel, dim3((Tu + 255) / 256, P), dim3(256), lds64, st, kwd, kwd_mask, utt,
+                           utt_mask, pair_utt, pair_kwd, n_pairs, sel, p0, out, B, K, L, Tk, Tu);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(sim_f32_pairs_kernel, dim3(Tk, P), dim3(256), (size_t)L * E * 4, st, kwd, kwd_mask, utt, utt_mask,
+                       pair_utt, pair_kwd, n_pairs, sel, p0, out, B, K, L, Tk, Tu, E);
     return hipGetLastError();
 }
 

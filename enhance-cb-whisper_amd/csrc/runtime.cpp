@@ -1587,16 +1587,53 @@ struct ConvInputStats {
     }
 };
 
-// the fp32 re-scoring network over selected pairs; logits null: no classifier (statistics only)
-int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask, int K,
-                 int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
-                 hipStream_t st, ConvInputStats* stats) {
-    if (!h->finalized || h->stem32.cout == 0) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no fp32 path)");
-    if (K < 0 || n_sel < 0 || n_sel > K || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
-    if (n_sel == 0) return CBW_OK;
-    if (ws_bytes < cbw_kws_rescore_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
+// The utterances and the pair list of a re-scoring call: utt f32 [B][L][Tu][E], and sel indexes the P pairs, which
+// are the rows of logits; pair q = (pair_utt[q], pair_kwd[q]) (device int32 [P]) or, both null, q = b * K + k.  The
+// per-utterance entry points are one_utterance(K): B = 1, no index arrays, pair q = keyword q.
+struct RescorePairs {
+    int B;
+    const int32_t *pair_utt, *pair_kwd;
+    int P;
+    bool single() const { return B == 1 && !pair_utt; }
+};
+RescorePairs one_utterance(int K) { return {1, nullptr, nullptr, K}; }
+
+// the argument checks of cbw_kws_rescore_pairs / cbw_kws_rescore_x3_pairs
+int check_rescore_pairs(const RescorePairs& pr, int K, int n_sel) {
+    if (pr.B < 1 || pr.P < 0 || K < 0) return fail(CBW_ERR_INVALID, "bad B/K/P");
+    if (n_sel > pr.P) return fail(CBW_ERR_INVALID, "n_sel exceeds the P pairs sel indexes");
+    if (pr.P == 0) return CBW_OK;   // an empty pair list needs no index arrays (then n_sel <= 0: nothing is launched)
+    if (K < 1) return fail(CBW_ERR_INVALID, "pairs given but no keywords");
+    if ((pr.pair_utt == nullptr) != (pr.pair_kwd == nullptr))
+        return fail(CBW_ERR_INVALID, "pair_utt and pair_kwd must both be given or both be null");
+    if (!pr.pair_utt && (int64_t)pr.P != (int64_t)pr.B * K)
+        return fail(CBW_ERR_INVALID, "without index arrays P must be B * K (every utterance against every keyword)");
+    return CBW_OK;
+}
+
+// the fp32 similarity maps of pairs sel[c0 .. c0 + cn) of a pass: the per-utterance kernels for one utterance (their
+// launches are what they were), the pair kernels otherwise
+int sim_f32_pass(const cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
+                 int K, const RescorePairs& pr, const int32_t* sel, int c0, int cn, float* maps, int Tk, int Tu,
+                 hipStream_t st) {
     const int L = h->cfg.n_layers;
     const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
+    if (pr.single())
+        HIPCHK(cbw_sim_f32(kwd, kwd_mask, utt, utt_mask, sel, c0, cn, maps, L, Tk, Tu, E, st));
+    else
+        HIPCHK(cbw_sim_f32_pairs(kwd, kwd_mask, K, utt, utt_mask, pr.B, pr.pair_utt, pr.pair_kwd, pr.P, sel, c0, cn, maps,
+                                 L, Tk, Tu, E, st));
+    return CBW_OK;
+}
+
+// the fp32 re-scoring network over selected pairs; logits null: no classifier (statistics only)
+int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask, int K,
+                 const RescorePairs& pr, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws,
+                 int64_t ws_bytes, hipStream_t st, ConvInputStats* stats) {
+    if (!h->finalized || h->stem32.cout == 0) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no fp32 path)");
+    if (K < 0 || n_sel < 0 || n_sel > pr.P || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
+    if (n_sel == 0) return CBW_OK;
+    if (ws_bytes < cbw_kws_rescore_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
     const ExactPlan plan = exact_plan(h, Tk, Tu, EXACT_CHUNK);
     char* p = (char*)ws;
     float* maps = (float*)p; p += align_up(plan.maps * 4);
@@ -1613,7 +1650,8 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
     // for the previous one.  Not while the stream is being captured (the call stays graph-capturable); results
     // unchanged.  Round 6: with 128 passes (~7 700 dispatches) in flight the one-call audit under --pmc still failed
     // (unspecified launch failure, 3 956 dispatches incomplete: profiles/r06b_pmc_f32_one_call_throttle128.log.txt),
-    // so the bound is the r05b passes' ~1 000 dispatches.
+    // so the bound is the r05b passes' ~1 000 dispatches.  The pairs form (cbw_kws_rescore_pairs) runs the same passes
+    // over its selected pairs, whatever their utterances: the throttle applies to it unchanged.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(hipStreamIsCapturing(st, &cap));
     const bool throttle = cap == hipStreamCaptureStatusNone && n_sel > RESCORE_THROTTLE * EXACT_CHUNK;
@@ -1628,7 +1666,7 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
             if (pass >= 2 * RESCORE_THROTTLE) HIPCHK(hipEventSynchronize(h->throttle_ev[k]));
             HIPCHK(hipEventRecord(h->throttle_ev[k], st));
         }
-        HIPCHK(cbw_sim_f32(kwd, kwd_mask, utt, utt_mask, sel, c0, cn, maps, L, Tk, Tu, E, st));
+        CHK(sim_f32_pass(h, utt, utt_mask, kwd, kwd_mask, K, pr, sel, c0, cn, maps, Tk, Tu, st));
         if (stats) CHK(stats->add(0, maps, (int64_t)cn * Tk * Tu, st));
         const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
         CHK(launch_conv32(h->stem32, maps, cn, Tk, Tu, stem, nullptr, true, st));
@@ -1736,7 +1774,20 @@ int cbw_kws_rescore(cbw_kws* h, const float* utt, const float* utt_mask, const f
                     cbw_stream_t stream) {
     if (!h || !utt || !utt_mask || !kwd || !kwd_mask || !logits || (n_sel > 0 && !sel))
         return fail(CBW_ERR_INVALID, "null argument");
-    return rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, Tk, Tu, sel, n_sel, logits, ws, ws_bytes,
+    return rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, one_utterance(K), Tk, Tu, sel, n_sel, logits, ws, ws_bytes,
+                        (hipStream_t)stream, nullptr);
+}
+
+int cbw_kws_rescore_pairs(cbw_kws* h, const float* utt, const float* utt_mask, int B, const float* kwd,
+                          const float* kwd_mask, int K, int Tk, int Tu, const int32_t* pair_utt, const int32_t* pair_kwd,
+                          int P, const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                          cbw_stream_t stream) {
+    if (!h) return fail(CBW_ERR_INVALID, "null handle");
+    const RescorePairs pr{B, pair_utt, pair_kwd, P};
+    CHK(check_rescore_pairs(pr, K, n_sel));
+    if (n_sel > 0 && (!utt || !utt_mask || !kwd || !kwd_mask || !logits || !sel))
+        return fail(CBW_ERR_INVALID, "null argument");
+    return rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, pr, Tk, Tu, sel, n_sel, logits, ws, ws_bytes,
                         (hipStream_t)stream, nullptr);
 }
 
@@ -1768,7 +1819,8 @@ int cbw_kws_calibrate_bias(cbw_kws* h, const float* utt, const float* utt_mask, 
     if (!utt || !utt_mask || !kwd || !kwd_mask || !sel) return fail(CBW_ERR_INVALID, "null argument");
     ConvInputStats s;
     CHK(s.init(h, st));
-    CHK(rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, Tk, Tu, sel, n_sel, nullptr, ws, ws_bytes, st, &s));
+    CHK(rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, one_utterance(K), Tk, Tu, sel, n_sel, nullptr, ws, ws_bytes, st,
+                     &s));
     HIPCHK(hipStreamSynchronize(st));
     std::vector<std::vector<double>> m;
     CHK(s.means(m));
@@ -1794,7 +1846,8 @@ int cbw_kws_calibrate_fp8(cbw_kws* h, const float* utt, const float* utt_mask, c
     s.amax = amax.as<float>();
     // + the conv inputs' channel sums (the bias correction of the e4m3 weights), points as cbw_kws_calibrate_bias
     CHK(s.init(h, st));
-    CHK(rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, Tk, Tu, sel, n_sel, nullptr, ws, ws_bytes, st, &s));
+    CHK(rescore_impl(h, utt, utt_mask, kwd, kwd_mask, K, one_utterance(K), Tk, Tu, sel, n_sel, nullptr, ws, ws_bytes, st,
+                     &s));
     HIPCHK(hipStreamSynchronize(st));
     std::vector<float> host(nb * 4 * G);
     HIPCHK(hipMemcpy(host.data(), amax.p, host.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1859,19 +1912,16 @@ int64_t cbw_kws_rescore_x3_workspace_bytes(cbw_kws* h, int Tk, int Tu) {
                      2 * align_up(p.small * 4));
 }
 
-int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
-                       int K, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
-                       cbw_stream_t stream) {
-    if (!h || !utt || !utt_mask || !kwd || !kwd_mask || !logits || (n_sel > 0 && !sel))
-        return fail(CBW_ERR_INVALID, "null argument");
+// the compensated re-scoring network over selected pairs (cbw_kws_rescore_x3, cbw_kws_rescore_x3_pairs)
+static int rescore_x3_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
+                           int K, const RescorePairs& pr, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits,
+                           void* ws, int64_t ws_bytes, hipStream_t st) {
     if (!h->finalized || h->stem32.cout == 0 || h->blocks3.empty())
         return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no re-scoring path)");
-    if (K < 0 || n_sel < 0 || n_sel > K || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
+    if (K < 0 || n_sel < 0 || n_sel > pr.P || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
     if (n_sel == 0) return CBW_OK;
     if (ws_bytes < cbw_kws_rescore_x3_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     const int L = h->cfg.n_layers;
-    const int E = h->cfg.variant == 0 ? h->cfg.embedding_dim : h->cfg.proj_units;
     const ExactPlan plan = exact_plan(h, Tk, Tu, x3_chunk());
     char* p = (char*)ws;
     float* maps = (float*)p; p += align_up(plan.maps * 4);
@@ -1890,7 +1940,7 @@ int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, cons
         // similarity maps in fp32, then the stem + max-pool: compensated bf16 in one pass (maps split into
         // [hi | hi | lo] channels of an NHWC16 image, cbw_stem16_pool_x3; CBW_X3_STEM32=1 or 3 L > 16: the fp32
         // stem, max-pool and split)
-        HIPCHK(cbw_sim_f32(kwd, kwd_mask, utt, utt_mask, sel, c0, cn, maps, L, Tk, Tu, E, st));
+        CHK(sim_f32_pass(h, utt, utt_mask, kwd, kwd_mask, K, pr, sel, c0, cn, maps, Tk, Tu, st));
         const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
         int H = out_dim(Hs, 3, 2), W = out_dim(Ws, 3, 2), C = 64;
         if (h->stem16x3_w.p && !x3_stem32()) {
@@ -1938,6 +1988,28 @@ int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, cons
         HIPCHK(cbw_pool_fc_f32(X32, h->fc_w.as<float>(), h->fc_b.as<float>(), sel, c0, cn, logits, H * W, C, st));
     }
     return CBW_OK;
+}
+
+int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
+                       int K, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                       cbw_stream_t stream) {
+    if (!h || !utt || !utt_mask || !kwd || !kwd_mask || !logits || (n_sel > 0 && !sel))
+        return fail(CBW_ERR_INVALID, "null argument");
+    return rescore_x3_impl(h, utt, utt_mask, kwd, kwd_mask, K, one_utterance(K), Tk, Tu, sel, n_sel, logits, ws, ws_bytes,
+                           (hipStream_t)stream);
+}
+
+int cbw_kws_rescore_x3_pairs(cbw_kws* h, const float* utt, const float* utt_mask, int B, const float* kwd,
+                             const float* kwd_mask, int K, int Tk, int Tu, const int32_t* pair_utt,
+                             const int32_t* pair_kwd, int P, const int32_t* sel, int n_sel, float* logits, void* ws,
+                             int64_t ws_bytes, cbw_stream_t stream) {
+    if (!h) return fail(CBW_ERR_INVALID, "null handle");
+    const RescorePairs pr{B, pair_utt, pair_kwd, P};
+    CHK(check_rescore_pairs(pr, K, n_sel));
+    if (n_sel > 0 && (!utt || !utt_mask || !kwd || !kwd_mask || !logits || !sel))
+        return fail(CBW_ERR_INVALID, "null argument");
+    return rescore_x3_impl(h, utt, utt_mask, kwd, kwd_mask, K, pr, Tk, Tu, sel, n_sel, logits, ws, ws_bytes,
+                           (hipStream_t)stream);
 }
 
 int cbw_kws_spot(const float* logits, const float* ghost, int K, float thr, int mode, float* prob, int32_t* idx,

@@ -194,8 +194,19 @@ class KWSModel:
                 logits = self._rescore_band(eng, kwd, km, utt, um, pkm, pum, logits)
         else:  # training-style batches: one utterance per keyword
             pair = torch.arange(K, dtype=torch.int32, device=dev)
-            out = eng.score_pairs(pu, pum, pk, pkm, pair, pair, features=return_features, trusted=True)
-            logits, feats = out if return_features else (out, None)
+            if self._band_active() > 0 and K > 0:
+                # the exact decisions of the Bu == 1 branch for the identity pair list: every pair in bf16, the
+                # band's pairs in fp32 (no compensated tier: the logits equal the K single-pair forwards')
+                pk32, _ = self._project(eng, kwd, km, f32=True)
+                pu32, _ = self._project(eng, utt, um, f32=True)
+                if self._band_auto and self.band_calibration is None:   # scored below by the corrected network
+                    self._calibrate_band(eng, pu[0], pum[0], pu32[0], pk, pkm, pk32)
+                out = eng.score_pairs_exact(pu, pum, pk, pkm, pu32, pk32, pair, pair, self.hparams.threshold,
+                                            self.exact_band, trusted=True, features=return_features)
+                logits, feats = (out[0], out[2]) if return_features else (out[0], None)
+            else:
+                out = eng.score_pairs(pu, pum, pk, pkm, pair, pair, features=return_features, trusted=True)
+                logits, feats = out if return_features else (out, None)
         loss = None
         if labels is not None:
             loss = torch.nn.functional.cross_entropy(logits, labels.to(dev).view(-1))

@@ -152,6 +152,30 @@ int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, cons
                        int K, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws,
                        int64_t ws_bytes, cbw_stream_t stream);
 
+/* the two re-scoring tiers for a list of (utterance, keyword) pairs: the exact decisions of the paired batch of
+ * efficient_kws/model.py:171-184 (utt batch == n_keywords, pair i = (utterance i, keyword i)) and of batches of
+ * utterances against one keyword list decided by model.py:782-813, where cbw_kws_rescore / cbw_kws_rescore_x3
+ * take one utterance.  utt f32 [B][L][Tu][E], utt_mask f32 [B][L][Tu], kwd / kwd_mask as cbw_kws_rescore
+ * (cbw_kws_project_f32's outputs); pair p = (pair_utt[p], pair_kwd[p]) (device int32 [P]); both NULL = every
+ * utterance against every keyword, p = b * K + k, and P must be B * K (the layout of cbw_kws_score_pairs).
+ *   logits[sel[i]] (f32 [P][2], one row per pair) <- the tier's logits of pair sel[i] (device int32 [n_sel],
+ *   indices into the P pairs).  A pair's logits are bit-identical to the per-utterance call's for that utterance
+ *   and keyword; rows not selected are not written.  sel and the pair indices are clamped into range on the
+ *   device before an operand is read; the logits row written is sel[i] itself, so sel must be valid.
+ * CBW_ERR_INVALID: B < 1, n_sel > P, one index array NULL and the other not, P != B * K without index arrays.
+ * P == 0 or n_sel == 0 returns CBW_OK and writes nothing.  Workspace: cbw_kws_rescore_workspace_bytes /
+ * cbw_kws_rescore_x3_workspace_bytes (a pass's size does not depend on B).  The host-blocking dispatch throttle
+ * of cbw_kws_rescore applies to cbw_kws_rescore_pairs unchanged: outside graph capture, a call over more than
+ * 256 selected pairs waits on the host so that at most 16 passes are in flight.  n_layers <= 4 only.         */
+int cbw_kws_rescore_pairs(cbw_kws* h, const float* utt, const float* utt_mask, int B, const float* kwd,
+                          const float* kwd_mask, int K, int Tk, int Tu, const int32_t* pair_utt, const int32_t* pair_kwd,
+                          int P, const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                          cbw_stream_t stream);
+int cbw_kws_rescore_x3_pairs(cbw_kws* h, const float* utt, const float* utt_mask, int B, const float* kwd,
+                             const float* kwd_mask, int K, int Tk, int Tu, const int32_t* pair_utt,
+                             const int32_t* pair_kwd, int P, const int32_t* sel, int n_sel, float* logits, void* ws,
+                             int64_t ws_bytes, cbw_stream_t stream);
+
 /* bias correction of the bf16 scoring network (setup, no counterpart in the reference: it only narrows the
  * bf16 error the exact tiers must cover).  Runs the fp32 network (cbw_kws_rescore's arguments and
  * workspace) over the n_sel calibration pairs, takes each conv's mean input per channel E[x_c], and sets
