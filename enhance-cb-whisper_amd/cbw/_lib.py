@@ -128,6 +128,15 @@ SIGNATURES = {
     "cbw_kws_fp8_scales": (c_int, [c_void_p, c_void_p, c_int]),
     "cbw_conv2d_fp8": (c_int, [c_void_p] * 5 + [c_float, c_void_p, c_float] + [c_int] * 9 + [c_void_p]),
     "cbw_fp8_probe": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "cbw_conv2d_f32": (c_int, [c_void_p] * 5 + [c_int] * 12 + [c_void_p]),
+    "cbw_sim_maps_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int,
+                                 c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cbw_maxpool_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "cbw_pool_fc_f32": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "cbw_split3_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "cbw_channel_sum_workspace_bytes": (c_int64, [c_int]),
+    "cbw_channel_sum_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "cbw_conv2d_x3": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
 }
 
 ERRORS = {-1: "CBW_ERR_INVALID", -2: "CBW_ERR_HIP", -3: "CBW_ERR_OOM", -4: "CBW_ERR_STATE", -5: "CBW_ERR_NOT_FOUND"}

@@ -421,10 +421,11 @@ int load_conv_bn_x3(const ParamStore& ps, const std::string& prefix, const ConvS
 // one conv of the compensated tier: x bf16 [N][H][W][2C] = [hi | lo] (c.cin = 3C K-channels), y per flags
 // (SPLIT3: bf16 [M][2 Cout] [hi | lo] + optional fp32 copy y32; OUT_F32: fp32 [M][Cout]); residual fp32
 // [M][Cout] (res_split false) or a [hi | lo] tensor (res_split true)
-int launch_conv_x3(const ConvW& c, const void* x, int N, int H, int W, void* y, float* y32, const void* res,
-                   bool res_split, int flags, const void* zero, hipStream_t st, Prof* prof) {
+// (w / bias: the conv's device operands, c.w / c.b of a loaded ConvW or the caller's for cbw_conv2d_x3)
+int launch_conv_x3(const ConvShape& c, const void* w, const float* bias, const void* x, int N, int H, int W, void* y,
+                   float* y32, const void* res, bool res_split, int flags, const void* zero, hipStream_t st, Prof* prof) {
     ConvArgs a{};
-    a.x = x; a.w = c.w.p; a.bias = c.b.as<float>(); a.res = res; a.y = y; a.y32 = y32; a.zero = zero;
+    a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y; a.y32 = y32; a.zero = zero;
     a.xfold = c.cin / 3; a.x_ld = 2 * (c.cin / 3);
     conv_geometry(a, c, N, H, W);
     a.res_ld = res_split ? 2 * c.cout : c.cout;
@@ -436,6 +437,10 @@ int launch_conv_x3(const ConvW& c, const void* x, int N, int H, int W, void* y, 
     HIPCHK(cbw_conv_igemm(a, st));
     // the compensated conv's GEMM: K over the three split segments; always tier 1
     return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel, 1);
+}
+int launch_conv_x3(const ConvW& c, const void* x, int N, int H, int W, void* y, float* y32, const void* res,
+                   bool res_split, int flags, const void* zero, hipStream_t st, Prof* prof) {
+    return launch_conv_x3(c, c.w.p, c.b.as<float>(), x, N, H, W, y, y32, res, res_split, flags, zero, st, prof);
 }
 
 int launch_conv32(const ConvW& c, const float* x, int N, int H, int W, float* y, const float* res, bool relu,
@@ -2976,6 +2981,96 @@ int cbw_conv1x1_dual(const uint16_t* x, const uint16_t* x2, const uint16_t* w, c
     a.flags = flags;
     HIPCHK(cbw_conv_igemm(a, (hipStream_t)stream));
     return CBW_OK;
+}
+
+// ---- the exact-decision tiers' kernels one by one (tests): argument checks, then the launcher the tier calls
+int cbw_conv2d_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W,
+                   int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw, int relu, cbw_stream_t stream) {
+    if (!x || !w || !y || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 64 || KH <= 0 || KW <= 0 ||
+        sh <= 0 || sw <= 0 || ph < 0 || pw < 0 || H + 2 * ph < KH || W + 2 * pw < KW)
+        return fail(CBW_ERR_INVALID, "cbw_conv2d_f32: null operand, empty shape or Cout % 64 != 0");
+    if (Cin % 16 == 0 && (((uintptr_t)x | (uintptr_t)w) & 15))
+        return fail(CBW_ERR_INVALID, "cbw_conv2d_f32: x and w must be 16-byte aligned when Cin % 16 == 0");
+    F32ConvArgs a{};
+    a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
+    a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
+    a.Ho = (H + 2 * ph - KH) / sh + 1;
+    a.Wo = (W + 2 * pw - KW) / sw + 1;
+    if ((int64_t)N * a.Ho * a.Wo > INT32_MAX / 64 || (int64_t)KH * KW * Cin > INT32_MAX / 64)
+        return fail(CBW_ERR_INVALID, "cbw_conv2d_f32: shape too large");
+    a.M = N * a.Ho * a.Wo;
+    a.relu = relu ? 1 : 0;
+    HIPCHK(cbw_conv_f32(a, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_sim_maps_f32(const float* utt, const float* utt_mask, int B, const float* kwd, const float* kwd_mask, int K,
+                     int L, int Tk, int Tu, int E, const int32_t* pair_utt, const int32_t* pair_kwd, int n_pairs,
+                     const int32_t* sel, int p0, int P, float* out, cbw_stream_t stream) {
+    if (!utt || !utt_mask || !kwd || !kwd_mask || !sel || !out || B < 0 || K < 1 || L < 1 || Tk < 1 || Tu < 1 || E < 4 ||
+        E % 4 || p0 < 0 || P < 1 || P > 65535 || (int64_t)L * E * 4 > 64 * 1024)
+        return fail(CBW_ERR_INVALID, "cbw_sim_maps_f32: null operand or bad shape (E % 4 == 0, 1 <= P <= 65535)");
+    if ((((uintptr_t)utt | (uintptr_t)kwd) & 15))
+        return fail(CBW_ERR_INVALID, "cbw_sim_maps_f32: utt and kwd must be 16-byte aligned");
+    if (B == 0) {
+        if (pair_utt || pair_kwd) return fail(CBW_ERR_INVALID, "cbw_sim_maps_f32: pair indices need B >= 1");
+        HIPCHK(cbw_sim_f32(kwd, kwd_mask, utt, utt_mask, sel, p0, P, out, L, Tk, Tu, E, (hipStream_t)stream));
+        return CBW_OK;
+    }
+    if ((pair_utt == nullptr) != (pair_kwd == nullptr) || n_pairs < 1 ||
+        (!pair_utt && (int64_t)n_pairs != (int64_t)B * K))
+        return fail(CBW_ERR_INVALID, "cbw_sim_maps_f32: both index arrays or neither, and then n_pairs == B * K");
+    HIPCHK(cbw_sim_f32_pairs(kwd, kwd_mask, K, utt, utt_mask, B, pair_utt, pair_kwd, n_pairs, sel, p0, P, out, L, Tk, Tu,
+                             E, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, cbw_stream_t stream) {
+    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(CBW_ERR_INVALID, "cbw_maxpool_f32: bad argument");
+    HIPCHK(cbw_maxpool_f32(x, y, N, H, W, C, out_dim(H, 3, 2), out_dim(W, 3, 2), (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_pool_fc_f32(const float* x, const float* w, const float* b, const int32_t* sel, int p0, int P, float* logits,
+                    int HW, int C, cbw_stream_t stream) {
+    if (!x || !w || !b || !sel || !logits || p0 < 0 || P <= 0 || HW <= 0 || C <= 0)
+        return fail(CBW_ERR_INVALID, "cbw_pool_fc_f32: bad argument");
+    HIPCHK(cbw_pool_fc_f32(x, w, b, sel, p0, P, logits, HW, C, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_split3_f32(const float* x, uint16_t* y, int64_t M, int C, cbw_stream_t stream) {
+    if (!x || !y || M <= 0 || C <= 0 || C % 4 || (((uintptr_t)x | (uintptr_t)y) & 15))
+        return fail(CBW_ERR_INVALID, "cbw_split3_f32: null or misaligned operand, or C % 4 != 0");
+    HIPCHK(cbw_split3(x, y, M, C, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int64_t cbw_channel_sum_workspace_bytes(int C) {
+    if (C <= 0) return fail(CBW_ERR_INVALID, "cbw_channel_sum_workspace_bytes: bad argument");
+    return (int64_t)cbw_channel_sum_groups() * C * (int64_t)sizeof(float);
+}
+
+int cbw_channel_sum_f32(const float* x, int64_t M, int C, float* part, int64_t part_bytes, cbw_stream_t stream) {
+    if (!x || !part || M <= 0 || C <= 0) return fail(CBW_ERR_INVALID, "cbw_channel_sum_f32: bad argument");
+    if (part_bytes < cbw_channel_sum_workspace_bytes(C)) return fail(CBW_ERR_OOM, "cbw_channel_sum_f32: part too small");
+    HIPCHK(cbw_channel_sum_f32(x, M, C, part, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_conv2d_x3(const uint16_t* x, const uint16_t* w, const float* bias, const void* res, int res_split, void* y,
+                  float* y32, int out_split, int N, int H, int W, int C, int Cout, int k, int stride, int relu,
+                  cbw_stream_t stream) {
+    if (!x || !w || !bias || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 64 || Cout <= 0 || Cout % 64 ||
+        (k != 1 && k != 3) || (stride != 1 && stride != 2) || (y32 && !out_split))
+        return fail(CBW_ERR_INVALID, "cbw_conv2d_x3: null operand, C or Cout not a multiple of 64, k not 1 / 3, stride "
+                                     "not 1 / 2, or y32 without the split output");
+    const void* zp = nullptr;
+    CHK(block_zero_page(&zp));
+    const ConvShape c{3 * C, Cout, k, stride, relu != 0};
+    return launch_conv_x3(c, w, bias, x, N, H, W, y, y32, res, res_split != 0,
+                          out_split ? CBW_EPI_SPLIT3 : CBW_EPI_OUT_F32, zp, (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

@@ -399,6 +399,54 @@ int cbw_gemm(const uint16_t* x, const uint16_t* w, const float* bias, const void
  * 64): qkv bf16 [B][T][3][H][64] with q pre-scaled by 1/8 -> out bf16 [B][T][H * 64], softmax in fp32. */
 int cbw_encoder_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int H, cbw_stream_t stream);
 
+/* The kernels of the exact-decision tiers (cbw_kws_rescore, cbw_kws_rescore_x3, cbw_kws_calibrate_bias) one by one
+ * (building blocks for the tests): each entry checks its arguments and calls the launcher the tier itself calls, so a
+ * test runs the tier's kernel at shapes the whole network never takes.  Asynchronous like the tiers; float4 operands
+ * (noted per entry) must be 16-byte aligned.
+ *
+ * fp32 conv on the fp32-input MFMA (every conv of cbw_kws_rescore), y = act(conv(x, w) + bias (+ res)): x f32 NHWC
+ * [N][H][W][Cin], w f32 [Cout][KH][KW][Cin], bias f32 [Cout] or NULL, res f32 [N][Ho][Wo][Cout] or NULL, y f32
+ * [N][Ho][Wo][Cout]; any kernel size, strides and pads as cbw_conv2d; relu 0/1; Cout % 64 == 0.  Cin % 16 == 0
+ * takes the float4 path (x, w aligned), any other Cin (the stem, Cin = n_layers) the element-wise one. */
+int cbw_conv2d_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W,
+                   int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw, int relu, cbw_stream_t stream);
+/* fp32 masked similarity maps of the re-scoring tiers, out f32 NHWC [P][Tk][Tu][L]; kwd f32 [K][L][Tk][E] and
+ * kwd_mask f32 [K][L][Tk] as cbw_kws_rescore; E % 4 == 0 (E == 64 with L * Tk * 260 <= 128 KB of LDS runs the
+ * keyword-stationary kernel, everything else the generic one); utt, kwd aligned.
+ *   B == 0, one utterance (cbw_kws_rescore): utt f32 [L][Tu][E], utt_mask f32 [L][Tu]; map p = keyword sel[p0 + p]
+ *     (device int32, every index must lie in [0, K): not clamped); pair_utt, pair_kwd NULL, n_pairs ignored.
+ *   B >= 1, a pair list (cbw_kws_rescore_pairs): utt f32 [B][L][Tu][E], utt_mask f32 [B][L][Tu]; map p = pair
+ *     sel[p0 + p] of the n_pairs pairs (pair_utt[q], pair_kwd[q]) (device int32 [n_pairs]); both NULL = q = b * K + k
+ *     and n_pairs must be B * K.  Indices are clamped into range on the device.
+ * 1 <= P <= 65535. */
+int cbw_sim_maps_f32(const float* utt, const float* utt_mask, int B, const float* kwd, const float* kwd_mask, int K,
+                     int L, int Tk, int Tu, int E, const int32_t* pair_utt, const int32_t* pair_kwd, int n_pairs,
+                     const int32_t* sel, int p0, int P, float* out, cbw_stream_t stream);
+/* MaxPool2d(3, 2, 1) of the fp32 tiers: x f32 NHWC [N][H][W][C] -> y f32 [N][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C]. */
+int cbw_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, cbw_stream_t stream);
+/* AdaptiveAvgPool(1) + Linear(C -> 2) of the fp32 tiers: x f32 [P][HW][C], w f32 [2][C], b f32 [2];
+ * logits[sel[p0 + p]] (f32 rows of 2) <- the logits of x[p]; rows sel does not name are not written. */
+int cbw_pool_fc_f32(const float* x, const float* w, const float* b, const int32_t* sel, int p0, int P, float* logits,
+                    int HW, int C, cbw_stream_t stream);
+/* The compensated tier's activation split: x f32 [M][C] -> y bf16 [M][2C] = [hi | lo], hi = bf16(x) (round to nearest
+ * even), lo = bf16(x - hi); C % 4 == 0, x and y aligned. */
+int cbw_split3_f32(const float* x, uint16_t* y, int64_t M, int C, cbw_stream_t stream);
+/* Per-channel sums of x f32 [M][C] (the statistics of cbw_kws_calibrate_bias): part f32 [G][C], part_bytes >=
+ * cbw_channel_sum_workspace_bytes(C) = G * C * 4; workgroup g ADDS the sum of its rows to part[g][c], so the channel
+ * sums are the column sums of a part the caller zeroed before the first call. */
+int64_t cbw_channel_sum_workspace_bytes(int C);
+int cbw_channel_sum_f32(const float* x, int64_t M, int C, float* part, int64_t part_bytes, cbw_stream_t stream);
+/* One conv of the compensated tier (cbw_kws_rescore_x3) over caller-built split operands, on the bf16 MFMA kernels
+ * with fp32 accumulation: x bf16 [N][H][W][2C] = [x_hi | x_lo], read as the K-segments [x_hi | x_hi | x_lo] against
+ * w bf16 [Cout][k][k][3C] = [w_hi | w_lo | w_hi] per tap (w_hi = bf16(w), w_lo = bf16(w - w_hi)), so the sum is
+ * x_hi.w_hi + x_hi.w_lo + x_lo.w_hi; v = act(sum + bias (+ res)), bias f32 [Cout].  res (or NULL): f32 [M][Cout]
+ * (res_split 0) or bf16 [M][2 Cout] = [hi | lo], added as hi + lo (res_split 1).  out_split 0: y f32 [M][Cout] = v,
+ * y32 NULL; out_split 1: y bf16 [M][2 Cout] = [bf16(v) | bf16(v - bf16(v))] and y32 (optional) f32 [M][Cout] = v.
+ * k 1 or 3 with pad k / 2, stride 1 or 2, relu 0/1; C % 64 == 0, Cout % 64 == 0. */
+int cbw_conv2d_x3(const uint16_t* x, const uint16_t* w, const float* bias, const void* res, int res_split, void* y,
+                  float* y32, int out_split, int N, int H, int W, int C, int Cout, int k, int stride, int relu,
+                  cbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

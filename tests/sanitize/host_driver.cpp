@@ -144,6 +144,46 @@ int main() {
     EXPECT(cbw_checksum(lg, 16, &sum, nullptr, 0, nullptr) == CBW_ERR_INVALID, "checksum null workspace");
     EXPECT(cbw_checksum((const char*)lg + 4, 8, &sum, lg, 1 << 20, nullptr) == CBW_ERR_INVALID, "checksum misaligned");
     EXPECT(cbw_checksum(lg, 16, &sum, lg, 0, nullptr) == CBW_ERR_OOM, "checksum workspace too small");
+    // the exact-decision tiers' kernels one by one: every argument check comes before the launch
+    alignas(16) float f[8] = {0.f};
+    uint16_t hb[8] = {0};
+    EXPECT(cbw_conv2d_f32(nullptr, f, nullptr, nullptr, f, 1, 4, 4, 16, 64, 1, 1, 1, 1, 0, 0, 0, nullptr) ==
+               CBW_ERR_INVALID, "conv2d_f32 null x");
+    EXPECT(cbw_conv2d_f32(f, f, nullptr, nullptr, f, 1, 4, 4, 16, 48, 1, 1, 1, 1, 0, 0, 0, nullptr) == CBW_ERR_INVALID,
+           "conv2d_f32 Cout % 64");
+    EXPECT(cbw_conv2d_f32(f, f, nullptr, nullptr, f, 1, 2, 2, 3, 64, 7, 7, 2, 2, 1, 1, 0, nullptr) == CBW_ERR_INVALID,
+           "conv2d_f32 kernel larger than the padded map");
+    EXPECT(cbw_conv2d_f32(f + 1, f, nullptr, nullptr, f, 1, 4, 4, 16, 64, 1, 1, 1, 1, 0, 0, 0, nullptr) ==
+               CBW_ERR_INVALID, "conv2d_f32 misaligned x on the float4 path");
+    EXPECT(cbw_sim_maps_f32(f, f, 0, f, f, 1, 3, 7, 7, 66, nullptr, nullptr, 0, ix, 0, 1, f, nullptr) == CBW_ERR_INVALID,
+           "sim_maps_f32 E % 4");
+    EXPECT(cbw_sim_maps_f32(f, f, 0, f, f, 1, 3, 7, 7, 64, nullptr, nullptr, 0, nullptr, 0, 1, f, nullptr) ==
+               CBW_ERR_INVALID, "sim_maps_f32 null sel");
+    EXPECT(cbw_sim_maps_f32(f, f, 0, f, f, 1, 3, 7, 7, 64, ix, ix, 1, ix, 0, 1, f, nullptr) == CBW_ERR_INVALID,
+           "sim_maps_f32 pair indices with B == 0");
+    EXPECT(cbw_sim_maps_f32(f, f, 2, f, f, 3, 3, 7, 7, 64, ix, nullptr, 2, ix, 0, 1, f, nullptr) == CBW_ERR_INVALID,
+           "sim_maps_f32 one index array");
+    EXPECT(cbw_sim_maps_f32(f, f, 2, f, f, 3, 3, 7, 7, 64, nullptr, nullptr, 5, ix, 0, 1, f, nullptr) == CBW_ERR_INVALID,
+           "sim_maps_f32 n_pairs != B * K without index arrays");
+    EXPECT(cbw_maxpool_f32(f, nullptr, 1, 4, 4, 4, nullptr) == CBW_ERR_INVALID, "maxpool_f32 null y");
+    EXPECT(cbw_maxpool_f32(f, f, 1, 0, 4, 4, nullptr) == CBW_ERR_INVALID, "maxpool_f32 H 0");
+    EXPECT(cbw_pool_fc_f32(f, f, f, nullptr, 0, 1, f, 4, 512, nullptr) == CBW_ERR_INVALID, "pool_fc_f32 null sel");
+    EXPECT(cbw_pool_fc_f32(f, f, f, ix, 0, 1, f, 0, 512, nullptr) == CBW_ERR_INVALID, "pool_fc_f32 HW 0");
+    EXPECT(cbw_split3_f32(f, hb, 1, 6, nullptr) == CBW_ERR_INVALID, "split3_f32 C % 4");
+    EXPECT(cbw_split3_f32(nullptr, hb, 1, 4, nullptr) == CBW_ERR_INVALID, "split3_f32 null x");
+    EXPECT(cbw_channel_sum_workspace_bytes(0) == CBW_ERR_INVALID, "channel_sum_workspace_bytes C 0");
+    EXPECT(cbw_channel_sum_workspace_bytes(3) > 0 && cbw_channel_sum_workspace_bytes(3) % 12 == 0,
+           "channel_sum_workspace_bytes whole rows");
+    EXPECT(cbw_channel_sum_f32(f, 0, 4, f, 1 << 20, nullptr) == CBW_ERR_INVALID, "channel_sum_f32 M 0");
+    EXPECT(cbw_channel_sum_f32(f, 4, 4, f, 16, nullptr) == CBW_ERR_OOM, "channel_sum_f32 part too small");
+    EXPECT(cbw_conv2d_x3(hb, hb, f, nullptr, 0, f, nullptr, 0, 1, 4, 4, 48, 64, 1, 1, 0, nullptr) == CBW_ERR_INVALID,
+           "conv2d_x3 C % 64");
+    EXPECT(cbw_conv2d_x3(hb, hb, f, nullptr, 0, f, nullptr, 0, 1, 4, 4, 64, 64, 5, 1, 0, nullptr) == CBW_ERR_INVALID,
+           "conv2d_x3 k 5");
+    EXPECT(cbw_conv2d_x3(hb, hb, nullptr, nullptr, 0, f, nullptr, 0, 1, 4, 4, 64, 64, 1, 1, 0, nullptr) ==
+               CBW_ERR_INVALID, "conv2d_x3 null bias");
+    EXPECT(cbw_conv2d_x3(hb, hb, f, nullptr, 0, f, f, 0, 1, 4, 4, 64, 64, 1, 1, 0, nullptr) == CBW_ERR_INVALID,
+           "conv2d_x3 y32 without the split output");
 
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);
