@@ -79,6 +79,17 @@ SIGNATURES = {
     "cbw_kws_score_resized_workspace_bytes": (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     "cbw_kws_score_resized": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "cbw_kws_build_exact": (c_int, [c_void_p]),
+    "cbw_kws_rescore_resized_workspace_bytes": (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "cbw_kws_rescore_resized": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                        c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "cbw_kws_rescore_resized_x3_workspace_bytes": (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "cbw_kws_rescore_resized_x3": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                           c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "cbw_kws_sim_rows_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     c_int, c_int, c_void_p, c_void_p]),
+    "cbw_kws_sim_resize_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                       c_int, c_int, c_void_p, c_void_p]),
     "cbw_mel": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "cbw_mel_long": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cbw_encoder_create": (c_int, [ctypes.POINTER(EncoderConfig), ctypes.POINTER(c_void_p)]),

@@ -68,6 +68,7 @@ class KwsEngine:
         self._ws = _lib.Workspace()
         self._ws_rescore = _lib.Workspace()   # the re-scoring tiers' own scratch: they may overlap scoring
         self._pws = _lib.Workspace()
+        self._exact_built = False
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -79,9 +80,27 @@ class KwsEngine:
 
     @property
     def has_fp32(self) -> bool:
-        """The fp32 / compensated re-scoring networks exist (cbw_kws_finalize builds them for n_layers <= 4, the
-        ResNet input channels the fp32 stem takes; every efficient_kws config uses 3)."""
+        """cbw_kws_finalize built the fp32 / compensated re-scoring networks: it does for n_layers <= 4 (every
+        efficient_kws config uses 3), the handles ``rescore`` / ``score_exact`` serve.  CB-Whisper's own 12-channel
+        spotter gets the same networks on request (``build_exact``) and reports them as ``has_exact_resized``."""
         return self.n_layers <= 4
+
+    @property
+    def has_exact_resized(self) -> bool:
+        """The exact tiers of the resized spotter (``rescore_resized`` / ``score_resized_exact``) are available: a
+        raw-hs engine whose fp32 and compensated networks exist, from cbw_kws_finalize or ``build_exact``."""
+        return self.variant == VARIANT_L and (self.has_fp32 or self._exact_built)
+
+    def build_exact(self) -> "KwsEngine":
+        """Build the fp32 and compensated networks of a raw-hs engine with more than 4 layers (cbw_kws_build_exact):
+        what cbw_kws_finalize leaves out for the 12-channel CNN, so that an engine that never re-scores pays
+        nothing.  Setup-time (synchronises); no work where they exist."""
+        if self.variant != VARIANT_L:
+            raise ValueError("build_exact serves the resized spotter: build the engine with learn_features=False")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cbw_kws_build_exact(self.h), "cbw_kws_build_exact")
+        self._exact_built = True
+        return self
 
     @property
     def feat_dim(self) -> int:
@@ -652,6 +671,87 @@ class KwsEngine:
                                                       _lib.stream_handle()), "cbw_kws_score_resized")
         return logits
 
+    def _packed_f32(self, kwd32_packed):
+        """A ``pack_keywords(..., dtype=torch.float32)`` pair as (rows f32 [L, R, D] on the device, host offsets,
+        device offsets, K)."""
+        rows, off = kwd32_packed
+        if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[0] != self.n_layers:
+            raise ValueError(f"the exact tiers take fp32 keyword rows [L, R, D] (pack_keywords(dtype=torch.float32)), "
+                             f"got {tuple(rows.shape)} {rows.dtype}")
+        off_host = off.to("cpu", torch.int32).contiguous()
+        return rows.to(self.device).contiguous(), off_host, off_host.to(self.device), off_host.numel() - 1
+
+    def rescore_resized(self, utt32: torch.Tensor, kwd32_packed, out_size: Tuple[int, int], logits: torch.Tensor,
+                        sel: torch.Tensor, tier: str = "f32", trusted: bool = False) -> torch.Tensor:
+        """The exact tiers of CB-Whisper's own spotter (cbw_kws_rescore_resized / cbw_kws_rescore_resized_x3;
+        cb_whisper.py:110-128 as the reference runs it, in fp32 from fp32 hidden states): the logits of the keywords
+        ``sel`` (int indices, any order) written into ``logits`` [K, 2] in place, every other row untouched.  utt32
+        f32 [L, Tu, D] and kwd32_packed = pack_keywords(..., dtype=torch.float32), both L2-normalised per frame.
+        tier "f32": fp32-input MFMA throughout; "x3": the compensated bf16 network.  ``build_exact`` first."""
+        if tier not in ("f32", "x3"):
+            raise ValueError(f"unknown re-scoring tier {tier}")
+        if not self.has_exact_resized:
+            raise _lib.CbwError("rescore_resized needs the fp32 networks: call KwsEngine.build_exact() first")
+        rows, off_host, off_dev, K = self._packed_f32(kwd32_packed)
+        utt = utt32.to(self.device).contiguous()
+        L, Tu, D = utt.shape
+        if utt.dtype != torch.float32 or L != self.n_layers or rows.shape[2] != D:
+            raise ValueError(f"shape mismatch: utt {tuple(utt.shape)} {utt.dtype} keyword rows {tuple(rows.shape)}")
+        sel = self._pair_index(sel, K, trusted, "sel")
+        n = sel.numel()
+        if n == 0:
+            return logits
+        if (tuple(logits.shape) != (K, 2) or logits.dtype != torch.float32 or not logits.is_contiguous()
+                or logits.device != self.device):
+            raise ValueError(f"rescore_resized: logits must be contiguous f32 [{K}, 2] on {self.device}, got "
+                             f"{tuple(logits.shape)} {logits.dtype}")
+        Ho, Wo = out_size
+        wsq, call = ((self.lib.cbw_kws_rescore_resized_workspace_bytes, self.lib.cbw_kws_rescore_resized)
+                     if tier == "f32" else
+                     (self.lib.cbw_kws_rescore_resized_x3_workspace_bytes, self.lib.cbw_kws_rescore_resized_x3))
+        with torch.cuda.device(self.device):
+            nb = wsq(self.h, off_host.data_ptr(), K, Tu, D, Ho, Wo)
+            if nb < 0:
+                raise ValueError(f"cbw_kws_rescore_resized ({tier}) workspace: bad arguments "
+                                 f"(K {K}, Tu {Tu}, D {D}, out {Ho} x {Wo})")
+            ws = self._ws_rescore.get(nb, self.device)
+            _lib.check(call(self.h, utt.data_ptr(), Tu, rows.data_ptr(), rows.shape[1], D, off_dev.data_ptr(),
+                            off_host.data_ptr(), K, Ho, Wo, sel.data_ptr(), n, logits.data_ptr(), ws.data_ptr(),
+                            ws.numel(), _lib.stream_handle()), f"cbw_kws_rescore_resized ({tier})")
+        return logits
+
+    def score_resized_exact(self, utt_hs: torch.Tensor, kwd_packed_bf16, kwd_packed_f32,
+                            out_size: Tuple[int, int] = (150, 750), band: float = 0.0,
+                            band_x3: Optional[float] = 1e-4, chunk: Optional[int] = None):
+        """``score_exact`` for CB-Whisper's own spotter, decision argmax(logits) == 1 <=> p > 0.5 (cb_whisper.py:128):
+        every keyword scored in bf16 (``score_resized``), the keywords within ``band`` of p = 0.5 re-scored from the
+        fp32 hidden states ``utt_hs`` [L, Tu, D] and the fp32 keyword rows ``kwd_packed_f32`` -- on the compensated
+        tier and then those still within ``band_x3`` in fp32, or with ``band_x3`` None all of them in fp32.  Keywords
+        outside ``band`` keep their bf16 logits, so the fp32 decision is reproduced as long as the bf16 error < band
+        and the compensated error < band_x3.
+
+        Returns (logits f32 [K, 2], stats) with ``score_exact``'s stats keys."""
+        logits = self.score_resized(utt_hs, kwd_packed_bf16, out_size, chunk=chunk)
+        K = logits.shape[0]
+        stats = {"band": 0, "fp32": 0, "bf16": K}
+        if band <= 0 or K == 0:
+            return logits, stats
+        sel, n = self.band(logits, 0.5, band)
+        stats["band"] = n
+        if n == 0:
+            return logits, stats
+        utt32 = utt_hs.to(self.device, torch.float32)
+        if band_x3 is None:
+            self.rescore_resized(utt32, kwd_packed_f32, out_size, logits, sel, trusted=True)
+            stats["fp32"] = n
+            return logits, stats
+        self.rescore_resized(utt32, kwd_packed_f32, out_size, logits, sel, tier="x3", trusted=True)
+        sel2, n2 = self.band(logits, 0.5, band_x3)
+        if n2:
+            self.rescore_resized(utt32, kwd_packed_f32, out_size, logits, sel2, trusted=True)
+        stats["fp32"] = n2
+        return logits, stats
+
     # ------------------------------------------------------------------ decision
     def spot(self, logits: torch.Tensor, ghost: Optional[torch.Tensor] = None, threshold: float = 0.5,
              mode: str = "threshold") -> Tuple[torch.Tensor, torch.Tensor]:
@@ -660,14 +760,15 @@ class KwsEngine:
         return spot(logits, ghost, threshold, mode)
 
 
-def pack_keywords(kwd_hs, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Ragged keyword hs (list of [L, Tk_k, D]) -> (bf16 [L, sum Tk, D] rows, int32 offsets [K + 1]):
-    keyword k is rows off[k] .. off[k + 1] - 1 of every layer."""
+def pack_keywords(kwd_hs, device=None, dtype: torch.dtype = torch.bfloat16) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Ragged keyword hs (list of [L, Tk_k, D]) -> (``dtype`` [L, sum Tk, D] rows, int32 offsets [K + 1]):
+    keyword k is rows off[k] .. off[k + 1] - 1 of every layer.  bf16 for ``score_resized``, torch.float32 for the
+    exact tiers (``rescore_resized``)."""
     if len(kwd_hs) == 0:
         raise ValueError("no keywords")
     t = [torch.as_tensor(k) for k in kwd_hs]
     lens = torch.tensor([0] + [k.shape[1] for k in t], dtype=torch.int64)
-    rows = torch.cat([k.to(device, torch.bfloat16) for k in t], dim=1)
+    rows = torch.cat([k.to(device, dtype) for k in t], dim=1)
     return rows, torch.cumsum(lens, 0).to(torch.int32)
 
 

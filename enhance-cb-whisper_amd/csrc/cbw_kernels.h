@@ -246,6 +246,15 @@ hipError_t cbw_sim_f32(const float* kwd, const float* kwd_mask, const float* utt
 hipError_t cbw_sim_f32_pairs(const float* kwd, const float* kwd_mask, int K, const float* utt, const float* utt_mask,
                              int B, const int32_t* pair_utt, const int32_t* pair_kwd, int n_pairs, const int* sel, int p0,
                              int P, float* out, int L, int Tk, int Tu, int E, hipStream_t st);
+// CB-Whisper's own spotter in fp32: utt f32 [L][Tu][D], kwd f32 [L][R][D] with keyword k on rows off[k] .. off[k+1]-1
+// (device int32 [K + 1]); map p of the pass = keyword sel[p0 + p] (clamped into [0, K), its rows into [0, R) and
+// its length to TkMax in the kernel).  rows f32 [P][L][TkMax][ld] (ld >= Tu): row t < Tk_k, column u < Tu written.
+// D % 16 == 0; fp32-input MFMA, k ascending.
+hipError_t cbw_sim_rows_f32(const float* utt, const float* kwd, const int* off, const int* sel, int p0, int P, int K,
+                            int R, int L, int Tu, int D, int TkMax, int ld, float* rows, hipStream_t st);
+// those rows resized bilinearly (cbw_sim_resize's arithmetic) to fp32 NHWC out [P][Ho][Wo][L]
+hipError_t cbw_sim_resize_f32(const float* rows, const int* off, const int* sel, int p0, int P, int K, int R, int L,
+                              int Tu, int TkMax, int ld, int Ho, int Wo, float* out, hipStream_t st);
 hipError_t cbw_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, hipStream_t st);
 hipError_t cbw_pool_fc_f32(const float* x, const float* w, const float* b, const int* sel, int p0, int P, float* logits,
                            int HW, int C, hipStream_t st);

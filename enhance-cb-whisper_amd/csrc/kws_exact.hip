@@ -8,6 +8,9 @@
 // similarity maps, MaxPool2d(3,2,1), AdaptiveAvgPool + Linear with a scatter into the logits, and the
 // projector's layout permute.  Reference: efficient_kws/model.py:143-193 (projector, time projector,
 // sim_matrix, masks) and resnet.py:51-58 + HF ResNetModel (the ResNet).
+// For CB-Whisper's own 12-channel spotter (model/cb_whisper.py:110-128) the front of the same tiers: the fp32
+// similarity rows of a device-side selection of ragged keywords (fp32-input MFMA) and their bilinear resize to fp32
+// NHWC maps (cb_whisper.py:196, :206).
 #include <algorithm>
 
 #include "cbw_common.h"
@@ -292,6 +295,144 @@ __global__ __launch_bounds__(256) void sim_f32_e64_pairs_kernel(const float* __r
                      utt_mask + (int64_t)b * L * Tu, out + (int64_t)p * Tk * Tu * L, kr, L, Tk, Tu);
 }
 
+// ---- CB-Whisper's own spotter in fp32 (model/cb_whisper.py:110-128, :189-210): the front of the re-scoring tiers
+// for the resized 12-channel maps.  Keywords are ragged: kwd f32 [L][R][D] with keyword k on rows off[k] ..
+// off[k + 1] - 1 of every layer (device int32 [K + 1]); map p of a pass is keyword sel[p0 + p], which only the
+// device knows, so both kernels resolve it themselves.  k is clamped into [0, K), its first row into [0, R) and its
+// length into [0, min(R - row, TkMax)] before any address is formed: a bad index or offset gives a wrong map, never
+// an out-of-range access.
+CBW_DEV void keyword_of_sel(const int* __restrict__ off, const int* __restrict__ sel, int i, int K, int R, int TkMax,
+                            int& row0, int& Tk) {
+    const int k = min(max(sel[i], 0), K - 1);
+    row0 = min(max(off[k], 0), R - 1);
+    Tk = min(max(off[k + 1] - off[k], 0), min(R - row0, TkMax));
+}
+
+// similarity rows (cb_whisper.py:196, matmul(kwd_hs, utt_hs^T) per layer): rows f32 [P][L][TkMax][ld], map p layer l
+// row t < Tk_k column u < Tu = kwd[l][off_k + t] . utt[l][u].  One 64 x 64 tile of one (map, layer) per block on the
+// fp32-input MFMA as conv_f32_kernel runs it: exact products, fp32 accumulation, k ascending; tile rows past Tk_k
+// and columns past Tu are loaded as zeros and not stored.  Grid (row tiles of TkMax x column tiles, L, P): a block
+// whose row tile lies beyond its keyword leaves before the first barrier.  D % 16 == 0.
+__global__ __launch_bounds__(256) void sim_rows_f32_kernel(const float* __restrict__ utt, const float* __restrict__ kwd,
+                                                           const int* __restrict__ off, const int* __restrict__ sel,
+                                                           int p0, int K, int R, int Tu, int D, int TkMax, int ld,
+                                                           float* __restrict__ rows) {
+    __shared__ float As[2][F_BK][F_BM + F_PAD];
+    __shared__ float Bs[2][F_BK][F_BN + F_PAD];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    const int nt_n = (Tu + F_BN - 1) / F_BN;
+    const int m0 = (blockIdx.x / nt_n) * F_BM, n0 = (blockIdx.x % nt_n) * F_BN;
+    const int l = blockIdx.y, p = blockIdx.z, L = gridDim.y;
+    int row0, Tk;
+    keyword_of_sel(off, sel, p0 + p, K, R, TkMax, row0, Tk);
+    if (m0 >= Tk) return;   // uniform over the block
+    const int nk = D / F_BK;
+    const int lr = tid >> 2, kq = (tid & 3) * 4;
+    const bool a_ok = m0 + lr < Tk, b_ok = n0 + lr < Tu;
+    const float* ap = kwd + ((int64_t)l * R + row0 + (a_ok ? m0 + lr : 0)) * D + kq;
+    const float* bp = utt + ((int64_t)l * Tu + (b_ok ? n0 + lr : 0)) * D + kq;
+
+    f32x4 ra, rb;
+    auto load = [&](int kt) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        ra = a_ok ? *(const f32x4*)(ap + kt * F_BK) : z;
+        rb = b_ok ? *(const f32x4*)(bp + kt * F_BK) : z;
+    };
+    auto store = [&](int buf) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            As[buf][kq + j][lr] = ra[j];
+            Bs[buf][kq + j][lr] = rb[j];
+        }
+    };
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    load(0);
+    store(0);
+    __syncthreads();
+    const int fr = lane & 15, fq = lane >> 4;
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) load(kt + 1);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            float av[2], bv[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) av[i] = As[buf][kk * 4 + fq][wm * 32 + i * 16 + fr];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bv[j] = Bs[buf][kk * 4 + fq][wn * 32 + j * 16 + fr];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if (kt + 1 < nk) store(buf ^ 1);
+        __syncthreads();
+    }
+    // D[m][n]: lane holds rows 4*fq + q (keyword frames), column fr (utterance frame) of each 16x16 tile
+    float* out = rows + ((int64_t)p * L + l) * TkMax * ld;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wn * 32 + j * 16 + fr;
+            if (n >= Tu) continue;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int m = m0 + wm * 32 + i * 16 + fq * 4 + q;
+                if (m < Tk) out[(int64_t)m * ld + n] = acc[i][j][q];
+            }
+        }
+}
+
+// source coordinate of output index dst: max(scale (dst + 0.5) - 0.5, 0) with the product and the difference rounded
+// one by one (no FMA contraction), as the float64 checker's fp32 coordinates are.  Near frame 1500 one ulp of the
+// coordinate is 1.2e-4 of a frame, which an fp32 map resolves (sim_resize_kernel's bf16 output does not).
+CBW_DEV float resize_src(float scale, int dst) {
+#pragma clang fp contract(off)
+    const float p = scale * ((float)dst + 0.5f);
+    return fmaxf(p - 0.5f, 0.f);
+}
+
+// bilinear resize of those rows to fp32 NHWC [P][Ho][Wo][L] (cb_whisper.py:206), the arithmetic of
+// kws_kernels.hip's sim_resize_kernel: PyTorch upsample_bilinear2d, align_corners=False, no antialias, scale =
+// in / out in fp32, src = max(scale (dst + 0.5) - 0.5, 0) (resize_src: rounded step by step), the neighbour clamped
+// to the last row / column.  One thread per output pixel writes its L channels.
+__global__ void sim_resize_f32_kernel(const float* __restrict__ rows, const int* __restrict__ off,
+                                      const int* __restrict__ sel, int p0, int P, int K, int R, int L, int Tu, int TkMax,
+                                      int ld, int Ho, int Wo, float* __restrict__ out) {
+    const int64_t total = (int64_t)P * Ho * Wo;
+    const float sx = (float)Tu / (float)Wo;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int j = (int)(i % Wo);
+        const int64_t r = i / Wo;
+        const int ii = (int)(r % Ho);
+        const int p = (int)(r / Ho);
+        int row0, Tk;
+        keyword_of_sel(off, sel, p0 + p, K, R, TkMax, row0, Tk);
+        float* o = out + i * L;
+        if (Tk < 1) {   // no frames (refused on the host): a zero map, no read
+            for (int l = 0; l < L; ++l) o[l] = 0.f;
+            continue;
+        }
+        const float sy = (float)Tk / (float)Ho;
+        const float fy = resize_src(sy, ii), fx = resize_src(sx, j);
+        const int y0 = min((int)fy, Tk - 1), x0 = min((int)fx, Tu - 1);
+        const int y1 = y0 + (y0 < Tk - 1 ? 1 : 0), x1 = x0 + (x0 < Tu - 1 ? 1 : 0);
+        const float ly1 = fy - y0, ly0 = 1.f - ly1, lx1 = fx - x0, lx0 = 1.f - lx1;
+        for (int l = 0; l < L; ++l) {
+            const float* s = rows + ((int64_t)p * L + l) * TkMax * ld;
+            o[l] = ly0 * (lx0 * s[(int64_t)y0 * ld + x0] + lx1 * s[(int64_t)y0 * ld + x1]) +
+                   ly1 * (lx0 * s[(int64_t)y1 * ld + x0] + lx1 * s[(int64_t)y1 * ld + x1]);
+        }
+    }
+}
+
 __global__ void maxpool_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C,
                                    int Ho, int Wo) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -459,6 +600,27 @@ hipError_t cbw_sim_f32_pairs(const float* kwd, const float* kwd_mask, int K, con
     }
     hipLaunchKernelGGL(sim_f32_pairs_kernel, dim3(Tk, P), dim3(256), (size_t)L * E * 4, st, kwd, kwd_mask, utt, utt_mask,
                        pair_utt, pair_kwd, n_pairs, sel, p0, out, B, K, L, Tk, Tu, E);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sim_rows_f32(const float* utt, const float* kwd, const int* off, const int* sel, int p0, int P, int K,
+                            int R, int L, int Tu, int D, int TkMax, int ld, float* rows, hipStream_t st) {
+    if (P <= 0 || P > 65535 || K < 1 || R < 1 || L < 1 || L > 65535 || Tu < 1 || D < F_BK || D % F_BK || TkMax < 1 ||
+        ld < Tu || p0 < 0)
+        return hipErrorInvalidValue;
+    const int tiles = ((TkMax + F_BM - 1) / F_BM) * ((Tu + F_BN - 1) / F_BN);
+    hipLaunchKernelGGL(sim_rows_f32_kernel, dim3(tiles, L, P), dim3(256), 0, st, utt, kwd, off, sel, p0, K, R, Tu, D,
+                       TkMax, ld, rows);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sim_resize_f32(const float* rows, const int* off, const int* sel, int p0, int P, int K, int R, int L,
+                              int Tu, int TkMax, int ld, int Ho, int Wo, float* out, hipStream_t st) {
+    if (P <= 0 || K < 1 || R < 1 || L < 1 || Tu < 1 || TkMax < 1 || ld < Tu || Ho < 1 || Wo < 1 || p0 < 0)
+        return hipErrorInvalidValue;
+    const int grid = (int)std::min<int64_t>(((int64_t)P * Ho * Wo + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(sim_resize_f32_kernel, dim3(grid), dim3(256), 0, st, rows, off, sel, p0, P, K, R, L, Tu, TkMax,
+                       ld, Ho, Wo, out);
     return hipGetLastError();
 }
 

@@ -1631,14 +1631,13 @@ int sim_f32_pass(const cbw_kws* h, const float* utt, const float* utt_mask, cons
     return CBW_OK;
 }
 
-// the fp32 re-scoring network over selected pairs; logits null: no classifier (statistics only)
-int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask, int K,
-                 const RescorePairs& pr, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws,
-                 int64_t ws_bytes, hipStream_t st, ConvInputStats* stats) {
-    if (!h->finalized || h->stem32.cout == 0) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no fp32 path)");
-    if (K < 0 || n_sel < 0 || n_sel > pr.P || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
-    if (n_sel == 0) return CBW_OK;
-    if (ws_bytes < cbw_kws_rescore_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
+// the fp32 re-scoring network over the n_sel > 0 selected maps of [Tk][Tu] pixels, in passes of EXACT_CHUNK;
+// fill(c0, cn, maps) writes the fp32 NHWC maps [cn][Tk][Tu][L] of sel[c0 .. c0 + cn) (sim_f32_pass for the
+// efficient_kws spotter, the similarity rows + resize for CB-Whisper's own); ws holds cbw_kws_rescore_workspace_bytes;
+// logits null: no classifier (statistics only)
+template <class Fill>
+int rescore_passes(cbw_kws* h, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws, hipStream_t st,
+                   ConvInputStats* stats, Fill&& fill) {
     const ExactPlan plan = exact_plan(h, Tk, Tu, EXACT_CHUNK);
     char* p = (char*)ws;
     float* maps = (float*)p; p += align_up(plan.maps * 4);
@@ -1671,7 +1670,7 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
             if (pass >= 2 * RESCORE_THROTTLE) HIPCHK(hipEventSynchronize(h->throttle_ev[k]));
             HIPCHK(hipEventRecord(h->throttle_ev[k], st));
         }
-        CHK(sim_f32_pass(h, utt, utt_mask, kwd, kwd_mask, K, pr, sel, c0, cn, maps, Tk, Tu, st));
+        CHK(fill(c0, cn, maps));
         if (stats) CHK(stats->add(0, maps, (int64_t)cn * Tk * Tu, st));
         const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
         CHK(launch_conv32(h->stem32, maps, cn, Tk, Tu, stem, nullptr, true, st));
@@ -1712,6 +1711,19 @@ int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const floa
             HIPCHK(cbw_pool_fc_f32(x, h->fc_w.as<float>(), h->fc_b.as<float>(), sel, c0, cn, logits, H * W, C, st));
     }
     return CBW_OK;
+}
+
+// the efficient_kws spotter's fp32 tier (cbw_kws_rescore, cbw_kws_rescore_pairs, the calibrations)
+int rescore_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask, int K,
+                 const RescorePairs& pr, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws,
+                 int64_t ws_bytes, hipStream_t st, ConvInputStats* stats) {
+    if (!h->finalized || h->stem32.cout == 0) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no fp32 path)");
+    if (K < 0 || n_sel < 0 || n_sel > pr.P || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
+    if (n_sel == 0) return CBW_OK;
+    if (ws_bytes < cbw_kws_rescore_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
+    return rescore_passes(h, Tk, Tu, sel, n_sel, logits, ws, st, stats, [&](int c0, int cn, float* maps) {
+        return sim_f32_pass(h, utt, utt_mask, kwd, kwd_mask, K, pr, sel, c0, cn, maps, Tk, Tu, st);
+    });
 }
 
 // the folded fp32 bias of a conv plus, with input channel means m, the bias correction
@@ -1910,24 +1922,26 @@ int x3_chunk() {
     return c;
 }
 
-int64_t cbw_kws_rescore_x3_workspace_bytes(cbw_kws* h, int Tk, int Tu) {
-    if (!h || !h->finalized || h->stem32.cout == 0 || h->blocks3.empty() || Tk <= 0 || Tu <= 0) return -1;
-    const ExactPlan p = exact_plan(h, Tk, Tu, x3_chunk());
+// the compensated tier's workspace for passes of `chunk` maps
+static int64_t x3_ws_bytes(const cbw_kws* h, int Tk, int Tu, int chunk) {
+    const ExactPlan p = exact_plan(h, Tk, Tu, chunk);
     return (int64_t)(align_up(p.maps * 4) + align_up(p.stem * 4) + 2 * align_up(p.big * 4) + 2 * align_up(p.big * 4) +
                      2 * align_up(p.small * 4));
 }
 
-// the compensated re-scoring network over selected pairs (cbw_kws_rescore_x3, cbw_kws_rescore_x3_pairs)
-static int rescore_x3_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
-                           int K, const RescorePairs& pr, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits,
-                           void* ws, int64_t ws_bytes, hipStream_t st) {
-    if (!h->finalized || h->stem32.cout == 0 || h->blocks3.empty())
-        return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no re-scoring path)");
-    if (K < 0 || n_sel < 0 || n_sel > pr.P || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
-    if (n_sel == 0) return CBW_OK;
-    if (ws_bytes < cbw_kws_rescore_x3_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
+int64_t cbw_kws_rescore_x3_workspace_bytes(cbw_kws* h, int Tk, int Tu) {
+    if (!h || !h->finalized || h->stem32.cout == 0 || h->blocks3.empty() || Tk <= 0 || Tu <= 0) return -1;
+    return x3_ws_bytes(h, Tk, Tu, x3_chunk());
+}
+
+// the compensated re-scoring network over the n_sel > 0 selected maps in passes of X3_CHUNK; fill as rescore_passes
+// takes it; ws holds x3_ws_bytes(h, Tk, Tu, X3_CHUNK)
+extern "C++" {
+template <class Fill>
+int rescore_x3_passes(cbw_kws* h, int Tk, int Tu, int X3_CHUNK, const int32_t* sel, int n_sel, float* logits, void* ws,
+                      hipStream_t st, Fill&& fill) {
     const int L = h->cfg.n_layers;
-    const ExactPlan plan = exact_plan(h, Tk, Tu, x3_chunk());
+    const ExactPlan plan = exact_plan(h, Tk, Tu, X3_CHUNK);
     char* p = (char*)ws;
     float* maps = (float*)p; p += align_up(plan.maps * 4);
     float* stem = (float*)p; p += align_up(plan.stem * 4);
@@ -1939,13 +1953,12 @@ static int rescore_x3_impl(cbw_kws* h, const float* utt, const float* utt_mask, 
     uint16_t* T2 = (uint16_t*)p;
     const void* zp = h->zero.p;
     const size_t nb = h->blocks3.size();
-    const int X3_CHUNK = x3_chunk();
     for (int c0 = 0; c0 < n_sel; c0 += X3_CHUNK) {
         const int cn = std::min(X3_CHUNK, n_sel - c0);
         // similarity maps in fp32, then the stem + max-pool: compensated bf16 in one pass (maps split into
         // [hi | hi | lo] channels of an NHWC16 image, cbw_stem16_pool_x3; CBW_X3_STEM32=1 or 3 L > 16: the fp32
         // stem, max-pool and split)
-        CHK(sim_f32_pass(h, utt, utt_mask, kwd, kwd_mask, K, pr, sel, c0, cn, maps, Tk, Tu, st));
+        CHK(fill(c0, cn, maps));
         const int Hs = out_dim(Tk, 7, 2), Ws = out_dim(Tu, 7, 2);
         int H = out_dim(Hs, 3, 2), W = out_dim(Ws, 3, 2), C = 64;
         if (h->stem16x3_w.p && !x3_stem32()) {
@@ -1994,6 +2007,21 @@ static int rescore_x3_impl(cbw_kws* h, const float* utt, const float* utt_mask, 
     }
     return CBW_OK;
 }
+}  // extern "C++"
+
+// the efficient_kws spotter's compensated tier (cbw_kws_rescore_x3, cbw_kws_rescore_x3_pairs)
+static int rescore_x3_impl(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
+                           int K, const RescorePairs& pr, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits,
+                           void* ws, int64_t ws_bytes, hipStream_t st) {
+    if (!h->finalized || h->stem32.cout == 0 || h->blocks3.empty())
+        return fail(CBW_ERR_STATE, "cbw_kws_finalize not called (or no re-scoring path)");
+    if (K < 0 || n_sel < 0 || n_sel > pr.P || Tk <= 0 || Tu <= 0) return fail(CBW_ERR_INVALID, "bad sizes");
+    if (n_sel == 0) return CBW_OK;
+    if (ws_bytes < cbw_kws_rescore_x3_workspace_bytes(h, Tk, Tu)) return fail(CBW_ERR_OOM, "workspace too small");
+    return rescore_x3_passes(h, Tk, Tu, x3_chunk(), sel, n_sel, logits, ws, st, [&](int c0, int cn, float* maps) {
+        return sim_f32_pass(h, utt, utt_mask, kwd, kwd_mask, K, pr, sel, c0, cn, maps, Tk, Tu, st);
+    });
+}
 
 int cbw_kws_rescore_x3(cbw_kws* h, const float* utt, const float* utt_mask, const float* kwd, const float* kwd_mask,
                        int K, int Tk, int Tu, const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
@@ -2015,6 +2043,136 @@ int cbw_kws_rescore_x3_pairs(cbw_kws* h, const float* utt, const float* utt_mask
         return fail(CBW_ERR_INVALID, "null argument");
     return rescore_x3_impl(h, utt, utt_mask, kwd, kwd_mask, K, pr, Tk, Tu, sel, n_sel, logits, ws, ws_bytes,
                            (hipStream_t)stream);
+}
+
+// ---- CB-Whisper's own spotter (cb_whisper.py:110-128): the exact tiers over the resized maps
+int cbw_kws_build_exact(cbw_kws* h) {
+    if (!h) return fail(CBW_ERR_INVALID, "null handle");
+    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
+    if (h->stem32.cout != 0 && !h->blocks3.empty()) return CBW_OK;   // cbw_kws_finalize (n_layers <= 4) or an earlier call
+    if (h->cfg.variant != 0) return fail(CBW_ERR_INVALID, "a projector's fp32 copy is built by cbw_kws_finalize");
+    HIPCHK(hipDeviceSynchronize());   // setup-time: no scoring may be in flight on any stream while the tiers appear
+    const int rc = build_f32(h);
+    if (rc != CBW_OK) {   // all or nothing: a half-built network must not pass for one
+        h->stem32 = ConvW{};
+        h->blocks32.clear();
+        h->blocks3.clear();
+        return rc;
+    }
+    HIPCHK(hipDeviceSynchronize());
+    return CBW_OK;
+}
+
+// pairs per compensated pass over resized maps: x3_chunk()'s 512 is sized for the efficient_kws maps (~21 MB of
+// workspace per pair); a (150, 750) map of 12 channels takes ~50 MB and up to ~14 MB of similarity rows, so 512 of them
+// would ask for ~32 GB.  64 keeps a pass near 4 GB, and its convs (M = 64 x 38 x 188 pixels and up) still fill the GPU.
+constexpr int RESIZED_X3_CHUNK = 64;
+static int resized_x3_chunk() { return std::min(x3_chunk(), RESIZED_X3_CHUNK); }
+
+struct ResizedExact {
+    int tk_max = 0, ld = 0;
+    int64_t rows_bytes = 0;   // one pass's similarity rows, f32 [chunk][L][tk_max][ld]
+};
+
+// the argument checks the two resized tiers share (cbw_kws_score_resized's, for fp32 rows) and the rows scratch
+static int resized_exact_args(const cbw_kws* h, const int32_t* off_host, int K, int Tu, int R, int D, int Ho, int Wo,
+                              int chunk, ResizedExact& r) {
+    if (h->cfg.variant != 0) return fail(CBW_ERR_INVALID, "the resized-similarity path takes raw hs (variant 0)");
+    if (D <= 0 || D % 16) return fail(CBW_ERR_INVALID, "D must be a multiple of 16");
+    if (!off_host || K < 0 || Tu <= 0 || R < 0) return fail(CBW_ERR_INVALID, "bad arguments");
+    if (off_host[0] < 0 || off_host[K] > R) return fail(CBW_ERR_INVALID, "keyword rows out of range");
+    r.tk_max = 0;
+    for (int k = 0; k < K; ++k) {
+        if (off_host[k + 1] <= off_host[k]) return fail(CBW_ERR_INVALID, "every keyword needs >= 1 frame");
+        r.tk_max = std::max(r.tk_max, off_host[k + 1] - off_host[k]);
+    }
+    if (Ho < 7 || Wo < 7) return fail(CBW_ERR_INVALID, "Ho and Wo must be >= 7 (the stem's kernel)");
+    r.ld = (Tu + 63) / 64 * 64;
+    r.rows_bytes = (int64_t)align_up((size_t)chunk * h->cfg.n_layers * std::max(r.tk_max, 1) * r.ld * 4);
+    return CBW_OK;
+}
+
+static int64_t resized_exact_ws(cbw_kws* h, const int32_t* off_host, int K, int Tu, int D, int Ho, int Wo, bool x3) {
+    if (!h || !h->finalized || h->stem32.cout == 0 || h->blocks3.empty() || !off_host || K < 0) return -1;
+    ResizedExact r;
+    const int chunk = x3 ? resized_x3_chunk() : EXACT_CHUNK;
+    if (resized_exact_args(h, off_host, K, Tu, off_host[K], D, Ho, Wo, chunk, r) != CBW_OK) return -1;
+    return r.rows_bytes + (x3 ? x3_ws_bytes(h, Ho, Wo, chunk) : cbw_kws_rescore_workspace_bytes(h, Ho, Wo));
+}
+
+int64_t cbw_kws_rescore_resized_workspace_bytes(cbw_kws* h, const int32_t* off_host, int K, int Tu, int D, int Ho,
+                                                int Wo) {
+    return resized_exact_ws(h, off_host, K, Tu, D, Ho, Wo, false);
+}
+
+int64_t cbw_kws_rescore_resized_x3_workspace_bytes(cbw_kws* h, const int32_t* off_host, int K, int Tu, int D, int Ho,
+                                                   int Wo) {
+    return resized_exact_ws(h, off_host, K, Tu, D, Ho, Wo, true);
+}
+
+static int rescore_resized_impl(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D,
+                                const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo,
+                                const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes, hipStream_t st,
+                                bool x3) {
+    if (!h) return fail(CBW_ERR_INVALID, "null handle");
+    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
+    ResizedExact r;
+    const int chunk = x3 ? resized_x3_chunk() : EXACT_CHUNK;
+    CHK(resized_exact_args(h, off_host, K, Tu, R, D, Ho, Wo, chunk, r));
+    if (h->stem32.cout == 0 || h->blocks3.empty())
+        return fail(CBW_ERR_STATE, "no fp32 network: call cbw_kws_build_exact first");
+    if (n_sel < 0) return fail(CBW_ERR_INVALID, "n_sel must be >= 0");
+    if (n_sel == 0) return CBW_OK;
+    if (K < 1) return fail(CBW_ERR_INVALID, "keywords selected but none given");
+    if (!utt || !kwd || !off_dev || !sel || !logits || !ws) return fail(CBW_ERR_INVALID, "null argument");
+    if ((uintptr_t)utt % 16 || (uintptr_t)kwd % 16) return fail(CBW_ERR_INVALID, "utt and kwd must be 16-byte aligned");
+    if (ws_bytes < resized_exact_ws(h, off_host, K, Tu, D, Ho, Wo, x3)) return fail(CBW_ERR_OOM, "workspace too small");
+    const int L = h->cfg.n_layers;
+    float* rows = (float*)ws;
+    void* tier_ws = (char*)ws + r.rows_bytes;
+    // a pass's maps: the similarity rows of its keywords (cb_whisper.py:196), resized to (Ho, Wo) (:206)
+    auto fill = [&](int c0, int cn, float* maps) {
+        HIPCHK(cbw_sim_rows_f32(utt, kwd, off_dev, sel, c0, cn, K, R, L, Tu, D, r.tk_max, r.ld, rows, st));
+        HIPCHK(cbw_sim_resize_f32(rows, off_dev, sel, c0, cn, K, R, L, Tu, r.tk_max, r.ld, Ho, Wo, maps, st));
+        return (int)CBW_OK;
+    };
+    if (x3) return rescore_x3_passes(h, Ho, Wo, chunk, sel, n_sel, logits, tier_ws, st, fill);
+    return rescore_passes(h, Ho, Wo, sel, n_sel, logits, tier_ws, st, nullptr, fill);
+}
+
+int cbw_kws_rescore_resized(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D, const int32_t* off_dev,
+                            const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel, int n_sel, float* logits,
+                            void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    return rescore_resized_impl(h, utt, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws, ws_bytes,
+                                (hipStream_t)stream, false);
+}
+
+int cbw_kws_rescore_resized_x3(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D,
+                               const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel,
+                               int n_sel, float* logits, void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    return rescore_resized_impl(h, utt, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws, ws_bytes,
+                                (hipStream_t)stream, true);
+}
+
+// the two stages one by one (tests): rows f32 [n_sel][L][tk_max][ld], then maps f32 NHWC [n_sel][Ho][Wo][L]
+int cbw_kws_sim_rows_f32(const float* utt, int Tu, const float* kwd, int R, int D, int L, const int32_t* off_dev, int K,
+                         const int32_t* sel, int n_sel, int tk_max, int ld, float* rows, cbw_stream_t stream) {
+    if (!utt || !kwd || !off_dev || !sel || !rows) return fail(CBW_ERR_INVALID, "null argument");
+    if (D <= 0 || D % 16) return fail(CBW_ERR_INVALID, "D must be a multiple of 16");
+    if (Tu < 1 || R < 1 || L < 1 || L > 16 || K < 1 || n_sel < 1 || n_sel > 65535 || tk_max < 1 || ld < Tu)
+        return fail(CBW_ERR_INVALID, "bad sizes");
+    if ((uintptr_t)utt % 16 || (uintptr_t)kwd % 16) return fail(CBW_ERR_INVALID, "utt and kwd must be 16-byte aligned");
+    HIPCHK(cbw_sim_rows_f32(utt, kwd, off_dev, sel, 0, n_sel, K, R, L, Tu, D, tk_max, ld, rows, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_kws_sim_resize_f32(const float* rows, int Tu, int R, int L, const int32_t* off_dev, int K, const int32_t* sel,
+                           int n_sel, int tk_max, int ld, int Ho, int Wo, float* maps, cbw_stream_t stream) {
+    if (!rows || !off_dev || !sel || !maps) return fail(CBW_ERR_INVALID, "null argument");
+    if (Tu < 1 || R < 1 || L < 1 || L > 16 || K < 1 || n_sel < 1 || tk_max < 1 || ld < Tu || Ho < 1 || Wo < 1)
+        return fail(CBW_ERR_INVALID, "bad sizes");
+    HIPCHK(cbw_sim_resize_f32(rows, off_dev, sel, 0, n_sel, K, R, L, Tu, tk_max, ld, Ho, Wo, maps, (hipStream_t)stream));
+    return CBW_OK;
 }
 
 int cbw_kws_spot(const float* logits, const float* ghost, int K, float thr, int mode, float* prob, int32_t* idx,

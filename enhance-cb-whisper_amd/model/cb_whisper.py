@@ -88,8 +88,10 @@ class CBWhisper:
     def __init__(self, dataset: str, split: str, root: str, kw_type: str, encoder_ckpt: str, whisper_ckpt: str,
                  kws_ckpt: str, language: str, prompt: bool = True, oracle: Union[bool, str] = "kws",
                  kws_features_size=(150, 750), keyword_prompt_prepend: str = "(", keyword_prompt_append: str = ")",
-                 keyword_separator: str = " ", keywords_per_group: int = 100, num_beams: int = 5):
-        """cb_whisper.py:21-80 (see the module docstring); every *_ckpt is a local directory / file."""
+                 keyword_separator: str = " ", keywords_per_group: int = 100, num_beams: int = 5,
+                 exact_band: Union[float, str, None] = None):
+        """cb_whisper.py:21-80 (see the module docstring); every *_ckpt is a local directory / file.  ``exact_band``
+        (not in the reference, whose spotters run in fp32): as ``from_components`` takes it."""
         from cbw.checkpoint import encoder_state, load_state_dict, read_json, whisper_configs
         from model.pba_whisper import PBAWhisper
         if isinstance(oracle, bool):
@@ -121,6 +123,7 @@ class CBWhisper:
         else:
             from model.model import KWSModel as CNNKWSModel
             self.cnn = CNNKWSModel.load_from_checkpoint(kws_ckpt)
+        self._set_band(self._default_band(exact_band))
 
     # ------------------------------------------------------------------ component constructor
     @classmethod
@@ -133,7 +136,7 @@ class CBWhisper:
                         layer_ids: Optional[Sequence[int]] = None, num_beams: int = 5, cnn=None,
                         keyword_hs: Optional[Sequence[torch.Tensor]] = None, kws_features_size=(150, 750),
                         keyword_feats32: Optional[torch.Tensor] = None,
-                        exact_band: Union[float, str] = "auto", fp8_band: Optional[float] = None,
+                        exact_band: Union[float, str, None] = None, fp8_band: Optional[float] = None,
                         segment_keywords: str = "union") -> "CBWhisper":
         """Already-built engines: the LEF spotter (``kws`` + the projected database keyword_feats /
         keyword_mask, bf16 [K, L, Tk', E] / f32 [K, L, Tk']) or the reference spotter (``cnn`` =
@@ -143,7 +146,11 @@ class CBWhisper:
         within ``exact_band`` of the argmax boundary (p = 0.5) are re-scored (KwsEngine.score_exact); "auto"
         measures the band on the engine's weights at the first spotted window (efficient_kws.model.calibrate_band).
         ``fp8_band`` (the engine's fp8 tier calibrated first, KwsEngine.calibrate_fp8): every pair is scored by the
-        e4m3 network and only the pairs within fp8_band of the boundary go on to bf16 and the exact tiers."""
+        e4m3 network and only the pairs within fp8_band of the boundary go on to bf16 and the exact tiers.
+        The reference spotter honours ``exact_band`` the same way from the fp32 hidden states
+        (KwsEngine.score_resized_exact): a number is used as given, "auto" measures the band at the first spotted
+        segment (``band_calibration``).  ``exact_band`` None is "auto" for the LEF spotter and 0, the bf16 pass
+        alone, for the reference spotter, whose fp32 networks are built only when a band asks for them."""
         if (cnn is None) == (kws is None):
             raise ValueError("give exactly one spotter: kws (LEF) or cnn (model.model.KWSModel)")
         self = cls.__new__(cls)
@@ -157,10 +164,16 @@ class CBWhisper:
         self.cnn, self.keyword_hs = cnn, keyword_hs
         self.keyword_feats, self.keyword_mask = keyword_feats, keyword_mask
         self.keyword_feats32 = keyword_feats32
-        self._set_band(exact_band)
+        self._set_band(self._default_band(exact_band))
         self.fp8_band = fp8_band
         self.segment_keywords = _check_segment_keywords(segment_keywords)
         return self
+
+    def _default_band(self, exact_band):
+        """None: "auto" for the LEF spotter, 0 (bf16 decisions, no fp32 networks built) for the CNN spotter."""
+        if exact_band is not None:
+            return exact_band
+        return 0.0 if self.cnn is not None else "auto"
 
     def _set_band(self, exact_band: Union[float, str]):
         """A number is used as given; "auto" starts at EXACT_BAND and is replaced by the band measured on these
@@ -192,7 +205,7 @@ class CBWhisper:
         self.fp8_band = None
         self.kw_database = None
         self._encoder_parts = None
-        self._packed = None
+        self._packed = self._packed32 = None
         self.oracle_buffer: List[str] = []
         self.last_spotted: List[List[str]] = []
         self.segment_keywords = "union"
@@ -227,8 +240,35 @@ class CBWhisper:
             frames = tuple(getattr(self.kws_model.hparams, "features_size", (150, 1500)))[0]
             pk, pm, _ = self.kw_database.db.projected(self.kws, frames)
             self.keyword_feats, self.keyword_mask = pk, pm
-            if self.exact_band > 0 and self.kws.has_fp32:   # no fp32 network for n_layers > 4: bf16 decisions
+            # the LEF engines have n_layers <= 4 and so their fp32 network from cbw_kws_finalize; the CNN spotter's
+            # 12-channel engine builds its own on request (spot_keywords, KwsEngine.build_exact)
+            if self.exact_band > 0 and self.kws.has_fp32:
                 self.keyword_feats32 = self.kw_database.db.projected_f32(self.kws, frames)
+
+    def _calibrate_cnn_band(self, utt_hs, packed16, packed32, size):
+        """exact_band "auto" for the CNN spotter, once, at the first spotted segment: the band is 2 x the largest
+        |p_bf16 - p_fp32| over up to 1024 keywords of that segment, by the rule and with the floors of
+        efficient_kws.model.calibrate_band (0.005, or EXACT_BAND with fewer than 256 keywords; at most 0.5).  No
+        bias calibration: the bf16 network keeps the reference biases."""
+        if not self._band_auto or self.band_calibration is not None or self.exact_band <= 0:
+            return
+        from efficient_kws.model import EXACT_BAND
+        eng = self.cnn.engine(int(utt_hs.shape[-1]))
+        if not eng.has_exact_resized:
+            eng.build_exact()
+        n = min(int(packed16[1].numel()) - 1, 1024)
+        end = int(packed16[1][n])
+        sub16 = (packed16[0][:, :end].contiguous(), packed16[1][: n + 1])
+        sub32 = (packed32[0][:, :end].contiguous(), packed32[1][: n + 1])
+        l16 = eng.score_resized(utt_hs, sub16, size)
+        l32 = torch.empty_like(l16)
+        eng.rescore_resized(utt_hs.to(torch.float32), sub32, size, l32,
+                            torch.arange(n, dtype=torch.int32, device=l16.device), trusted=True)
+        err = float((torch.softmax(l16.double(), -1)[:, 1] - torch.softmax(l32.double(), -1)[:, 1]).abs().max())
+        floor = 0.005 if n >= 256 else EXACT_BAND   # a small sample cannot narrow the default band
+        self.band_calibration = {"bias_calibration_pairs": 0, "held_out_pairs": n, "max_bf16_err": err,
+                                 "band": float(min(0.5, max(floor, 2.0 * err)))}
+        self.exact_band = self.band_calibration["band"]
 
     # ------------------------------------------------------------------ tokenizer
     def get_prompt_ids(self, text: str) -> List[int]:
@@ -261,15 +301,26 @@ class CBWhisper:
         out = []
         for s in range(S):
             if self.cnn is not None:
+                # exact_band > 0: the keywords near p = 0.5 re-scored in fp32 from the fp32 hidden states, as the
+                # reference evaluates every keyword (KwsEngine.score_resized_exact)
                 if self.kws_features_size is not None:
                     if self._packed is None:   # keyword rows packed once, resident on the GPU
                         self._packed = pack_keywords(self.keyword_hs, dev)
-                    idx = self.cnn.spot_keywords(hs[s], self._packed, self.kws_features_size)
+                    if self.exact_band > 0 and self._packed32 is None:   # the fp32 rows only when they are read
+                        self._packed32 = pack_keywords(self.keyword_hs, dev, dtype=torch.float32)
+                    self._calibrate_cnn_band(hs[s], self._packed, self._packed32, self.kws_features_size)
+                    idx = self.cnn.spot_keywords(hs[s], self._packed, self.kws_features_size,
+                                                 exact_band=self.exact_band, kwd_hs32=self._packed32)
                 else:   # cb_whisper.py:202-204: resize to (longest keyword of the group, utterance frames)
                     idx = []
                     for lo, hi in self._groups():
                         size = (max(int(h.shape[1]) for h in self.keyword_hs[lo:hi]), int(hs.shape[2]))
-                        idx += [lo + i for i in self.cnn.spot_keywords(hs[s], self.keyword_hs[lo:hi], size)]
+                        if self._band_auto and self.band_calibration is None and self.exact_band > 0:
+                            self._calibrate_cnn_band(hs[s], pack_keywords(self.keyword_hs[lo:hi], dev),
+                                                     pack_keywords(self.keyword_hs[lo:hi], dev, dtype=torch.float32),
+                                                     size)
+                        idx += [lo + i for i in self.cnn.spot_keywords(hs[s], self.keyword_hs[lo:hi], size,
+                                                                       exact_band=self.exact_band)]
             else:
                 ones = torch.ones((1, hs.shape[1], hs.shape[2]), device=dev)
                 u, um = self.kws.project(hs[s:s + 1], ones)

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from cbw.kws import KwsEngine, spot
+from cbw.kws import KwsEngine, pack_keywords, spot
 from cbw.synth import kws_param_shapes
 
 from .utils import KWSOutput
@@ -43,6 +43,7 @@ class KWSModel:
         self.hparams = SimpleNamespace(**hp)
         self._sd: Dict[str, torch.Tensor] = {}
         self._engine: Optional[KwsEngine] = None
+        self.last_exact_stats: Optional[dict] = None   # the cascade's counts of the last exact_band > 0 call
         self.training = False
 
     def _engine_hp(self, embedding_dim: int = 1024) -> dict:
@@ -104,15 +105,35 @@ class KWSModel:
 
     __call__ = forward
 
-    def score_keywords(self, utt_hs: torch.Tensor, kwd_hs, kws_features_size=(150, 750)) -> torch.Tensor:
+    def score_keywords(self, utt_hs: torch.Tensor, kwd_hs, kws_features_size=(150, 750), exact_band: float = 0.0,
+                       kwd_hs32=None, band_x3: Optional[float] = 1e-4) -> torch.Tensor:
         """cb_whisper.py:110-126 for one segment: utt_hs [12, Tu, D], kwd_hs a list of [12, Tk_k, D]
         (L2-normalised) or its packed form (cbw.kws.pack_keywords) -> logits [K, 2] (sims, resize, CNN
-        fused on the GPU)."""
+        fused on the GPU).  ``exact_band`` 0 (the default): the bf16 pass alone.  > 0: the keywords whose bf16
+        probability lies within ``exact_band`` of the argmax boundary p = 0.5 are re-scored as the reference
+        evaluates them, in fp32 from the fp32 hidden states (KwsEngine.score_resized_exact; the engine's fp32
+        networks are built on first use).  ``kwd_hs32``: the keywords packed in fp32
+        (pack_keywords(dtype=torch.float32)); needed when ``kwd_hs`` is already packed, bf16 rows having lost the
+        bits."""
         kh = kwd_hs if isinstance(kwd_hs, tuple) else list(kwd_hs)
-        return self.engine(int(utt_hs.shape[-1])).score_resized(utt_hs, kh, tuple(kws_features_size))
+        eng = self.engine(int(utt_hs.shape[-1]))
+        size = tuple(kws_features_size)
+        self.last_exact_stats = None
+        if not exact_band or exact_band <= 0:
+            return eng.score_resized(utt_hs, kh, size)
+        if kwd_hs32 is None:
+            if isinstance(kh, tuple):
+                raise ValueError("exact_band > 0 with packed bf16 keywords needs kwd_hs32, their fp32 packing")
+            kwd_hs32 = pack_keywords(kh, eng.device, dtype=torch.float32)
+        if not eng.has_exact_resized:
+            eng.build_exact()
+        logits, self.last_exact_stats = eng.score_resized_exact(utt_hs, kh, kwd_hs32, size, float(exact_band),
+                                                                band_x3=band_x3)
+        return logits
 
-    def spot_keywords(self, utt_hs: torch.Tensor, kwd_hs, kws_features_size=(150, 750)) -> List[int]:
-        """cb_whisper.py:128: indices with argmax(logits) == 1."""
-        logits = self.score_keywords(utt_hs, kwd_hs, kws_features_size)
+    def spot_keywords(self, utt_hs: torch.Tensor, kwd_hs, kws_features_size=(150, 750), exact_band: float = 0.0,
+                      kwd_hs32=None, band_x3: Optional[float] = 1e-4) -> List[int]:
+        """cb_whisper.py:128: indices with argmax(logits) == 1; ``exact_band`` as ``score_keywords``."""
+        logits = self.score_keywords(utt_hs, kwd_hs, kws_features_size, exact_band, kwd_hs32, band_x3)
         _, idx = spot(logits, None, 0.5, mode="argmax")
         return idx.tolist()

@@ -176,6 +176,44 @@ int cbw_kws_rescore_x3_pairs(cbw_kws* h, const float* utt, const float* utt_mask
                              const int32_t* pair_kwd, int P, const int32_t* sel, int n_sel, float* logits, void* ws,
                              int64_t ws_bytes, cbw_stream_t stream);
 
+/* The exact tiers for CB-Whisper's own spotter.  The reference runs it in fp32 from fp32 hidden states
+ * (model/cb_whisper.py:110-128: per-layer inner products :196, resize to kws_features_size :206,
+ * Resnet(num_channels=12) model/model.py:55-58, argmax(logits) == 1 :128); cbw_kws_score_resized is its bf16 pass.
+ *
+ * cbw_kws_build_exact: the fp32 and compensated networks for a finalized variant-0 handle of any n_layers
+ * (cbw_kws_finalize builds them itself only for n_layers <= 4, so a 12-channel handle that never asks pays
+ * nothing).  Setup call: synchronises the device.  CBW_OK and no work where they already exist.               */
+int cbw_kws_build_exact(cbw_kws* h);
+/* cbw_kws_rescore_resized (fp32-input MFMA throughout) / cbw_kws_rescore_resized_x3 (compensated bf16, the fp32
+ * stem where 3 n_layers > 16): logits[sel[i]] (f32 [K][2]) <- the tier's logits of keyword sel[i] (device int32
+ * [n_sel], any order, repeats allowed); rows not selected are not written.  utt f32 [L][Tu][D]; kwd f32 [L][R][D]
+ * with keyword k on rows off[k] .. off[k+1]-1 (off_dev / off_host as cbw_kws_score_resized), both per-frame
+ * L2-normalised (cb_whisper.py:106, utils.py:195) and 16-byte aligned.  Per pass of 32 (fp32) / 64 (x3) keywords:
+ * similarity rows (cb_whisper.py:196; exact fp32 products, fp32 accumulation, k ascending), bilinear resize to
+ * (Ho, Wo) (cb_whisper.py:206; PyTorch upsample_bilinear2d, align_corners=False, no antialias) into fp32 NHWC
+ * maps, then the passes of cbw_kws_rescore / cbw_kws_rescore_x3 (shared code, its host-blocking dispatch throttle
+ * included).  sel is clamped into [0, K) on the device before an operand is read; the row written is sel[i]
+ * itself.  A keyword's logits do not depend on what else is selected.  Checked in this order: variant 0, D % 16,
+ * offsets in range and increasing, Ho, Wo >= 7 (CBW_ERR_INVALID), cbw_kws_build_exact called (CBW_ERR_STATE);
+ * n_sel == 0 then returns CBW_OK.  No allocation, no synchronisation outside the throttle.                     */
+int64_t cbw_kws_rescore_resized_workspace_bytes(cbw_kws* h, const int32_t* off_host, int K, int Tu, int D, int Ho,
+                                                int Wo);
+int cbw_kws_rescore_resized(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D, const int32_t* off_dev,
+                            const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel, int n_sel, float* logits,
+                            void* ws, int64_t ws_bytes, cbw_stream_t stream);
+int64_t cbw_kws_rescore_resized_x3_workspace_bytes(cbw_kws* h, const int32_t* off_host, int K, int Tu, int D, int Ho,
+                                                   int Wo);
+int cbw_kws_rescore_resized_x3(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D,
+                               const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel,
+                               int n_sel, float* logits, void* ws, int64_t ws_bytes, cbw_stream_t stream);
+/* the two stages of a pass one by one (tests): rows f32 [n_sel][L][tk_max][ld] (ld >= Tu; row t < Tk_k and column
+ * u < Tu of map i = keyword sel[i] written, cb_whisper.py:196), then maps f32 NHWC [n_sel][Ho][Wo][L]
+ * (cb_whisper.py:206).  tk_max bounds the keyword lengths read; D % 16 == 0, L <= 16.                           */
+int cbw_kws_sim_rows_f32(const float* utt, int Tu, const float* kwd, int R, int D, int L, const int32_t* off_dev, int K,
+                         const int32_t* sel, int n_sel, int tk_max, int ld, float* rows, cbw_stream_t stream);
+int cbw_kws_sim_resize_f32(const float* rows, int Tu, int R, int L, const int32_t* off_dev, int K, const int32_t* sel,
+                           int n_sel, int tk_max, int ld, int Ho, int Wo, float* maps, cbw_stream_t stream);
+
 /* bias correction of the bf16 scoring network (setup, no counterpart in the reference: it only narrows the
  * bf16 error the exact tiers must cover).  Runs the fp32 network (cbw_kws_rescore's arguments and
  * workspace) over the n_sel calibration pairs, takes each conv's mean input per channel E[x_c], and sets

@@ -1,4 +1,10 @@
-"""Time the fp32 re-scoring path (cbw_kws_rescore) on LEF pairs (large-v3 D, maps 75x750)."""
+"""Time the fp32 re-scoring path (cbw_kws_rescore) on LEF pairs (large-v3 D, maps 75x750).
+
+RS_MODE=cnn12: the exact tiers of CB-Whisper's own 12-channel spotter instead (cbw_kws_rescore_resized / _x3): RS_N
+ragged keywords (20-192 frames) of D 1280 against 1500 utterance frames, maps (150, 750); per tier the time per
+selected keyword, the share of it the fp32 front takes (similarity rows + resize, timed alone over the same passes of
+32), and the bf16 pass (cbw_kws_score_resized) over the same keywords beside them.  HIP events around RS_REPS calls
+after a warm-up call."""
 import os
 import sys
 import time
@@ -7,10 +13,79 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "enhance-cb-whisper_amd")]
-from cbw import synth  # noqa: E402
-from cbw.kws import KwsEngine  # noqa: E402
+from cbw import _lib, synth  # noqa: E402
+from cbw.kws import KwsEngine, pack_keywords  # noqa: E402
 
 N = int(os.environ.get("RS_N", "64"))
+
+
+def timed(fn, reps):
+    """Mean milliseconds of fn() over reps calls between two events, after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def cnn12():
+    reps = int(os.environ.get("RS_REPS", "3"))
+    L, D, Tu, size = 12, 1280, 1500, (150, 750)
+    hp = dict(n_layers=L, embedding_dim=D, learn_features=False, proj_mlp=False)
+    eng = KwsEngine(hp, synth.synth_kws_state_dict(seed=3, **hp)).build_exact()
+    d = eng.device
+    g = torch.Generator(device=d).manual_seed(0)
+    lens = torch.randint(20, 193, (N,), generator=torch.Generator().manual_seed(0)).tolist()
+    utt = torch.randn((L, Tu, D), generator=g, device=d)
+    utt = utt / utt.norm(dim=-1, keepdim=True)
+    kwd = []
+    for T in lens:
+        k = torch.randn((L, T, D), generator=g, device=d)
+        kwd.append(k / k.norm(dim=-1, keepdim=True))
+    p32 = pack_keywords(kwd, d, dtype=torch.float32)
+    p16 = pack_keywords(kwd, d)
+    del kwd
+    sel = torch.arange(N, device=d, dtype=torch.int32)
+    logits = torch.zeros((N, 2), device=d)
+    t16 = timed(lambda: eng.score_resized(utt, p16, size), reps)
+    print(f"cnn12 {N} keywords, mean {sum(lens) / N:.0f} frames: bf16 score_resized {t16:.1f} ms = {t16 / N:.3f} ms per "
+          f"keyword")
+    # the front alone, in the fp32 tier's passes of 32
+    rows_k, off = p32
+    off_dev = off.to(d)
+    tk_max, ld, P = max(lens), (Tu + 63) // 64 * 64, 32
+    rows = torch.empty((P, L, tk_max, ld), device=d)
+    maps = torch.empty((P, size[0], size[1], L), device=d)
+    st = _lib.stream_handle()
+
+    def front(resize=True):
+        for c0 in range(0, N, P):
+            cn = min(P, N - c0)
+            s = sel[c0:c0 + cn]
+            _lib.check(eng.lib.cbw_kws_sim_rows_f32(utt.data_ptr(), Tu, rows_k.data_ptr(), rows_k.shape[1], D, L,
+                                                    off_dev.data_ptr(), N, s.data_ptr(), cn, tk_max, ld, rows.data_ptr(),
+                                                    st), "cbw_kws_sim_rows_f32")
+            if resize:
+                _lib.check(eng.lib.cbw_kws_sim_resize_f32(rows.data_ptr(), Tu, rows_k.shape[1], L, off_dev.data_ptr(), N,
+                                                          s.data_ptr(), cn, tk_max, ld, size[0], size[1], maps.data_ptr(),
+                                                          st), "cbw_kws_sim_resize_f32")
+    tf, tr = timed(front, reps), timed(lambda: front(False), reps)
+    print(f"  fp32 front alone: {tf:.1f} ms = {tf / N:.3f} ms per keyword (similarity rows {tr / N:.3f}, resize "
+          f"{(tf - tr) / N:.3f})")
+    for tier in ("x3", "f32"):
+        t = timed(lambda: eng.rescore_resized(utt, p32, size, logits, sel, tier=tier, trusted=True), reps)
+        print(f"  tier {tier}: {t:.1f} ms = {t / N:.3f} ms per keyword; the front is {100 * tf / t:.0f} % of it; "
+              f"{t / t16:.1f} x the bf16 pass")
+
+
+if os.environ.get("RS_MODE") == "cnn12":
+    cnn12()
+    sys.exit(0)
+
 hp = dict(n_layers=3, embedding_dim=1280, learn_features=True, proj_mlp=True, frames_conv=True)
 eng = KwsEngine(hp, synth.synth_kws_state_dict(seed=0, **hp))
 d = eng.device
