@@ -49,6 +49,9 @@ struct ConvArgs {
     // channels [0, Cin = 3C) read physical channels c < C ? c : c - C, i.e. a [hi | lo] tensor (x_ld = 2C)
     // seen as [hi | hi | lo]
     int x_ld, xfold;
+    // conv_igemm_p8's 3x3 tiles (set by its launcher, see p8_rowmap.h): > 0 = tile rows in (group of p8_g pairs, oh,
+    // pair, ow) order with the all-padding kernel rows dropped from each tile's K loop; 0 = (pair, oh, ow) order
+    int p8_g;
 };
 
 hipError_t cbw_conv_igemm(const ConvArgs& a, hipStream_t st);

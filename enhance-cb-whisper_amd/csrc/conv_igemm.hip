@@ -21,6 +21,7 @@
 // stores run on 16-byte row vectors.
 #include "cbw_common.h"
 #include "cbw_kernels.h"
+#include "p8_rowmap.h"
 
 thread_local const char* cbw_last_conv_kernel = "";
 
@@ -801,16 +802,53 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
     const bf16* a2_px[2][NA];
     unsigned a_tm[2][NA];
     const bf16* wrow[2][NB];
+    // 3x3 tiles in row order (a.p8_g > 0, p8_rowmap.h): thread t decodes the tile's logical row t once into the still
+    // idle LDS -- (n, oh, ow, group), n = -1 past M -- for the eight lanes that gather that row, and the first and
+    // last valid rows give the tile-uniform K-tile range [kt_lo, kt_hi): kernel rows that are padding for every row
+    // of the tile are not walked.  The tap masks below stay and still decide every single load.
+    constexpr bool ROWS = KH * KW > 1;
+    bool rowmap = false;
+    int kh_lo = 0, kt_lo = 0, kt_hi = nk;
+    if constexpr (ROWS) {
+        rowmap = a.p8_g > 0;
+        if (rowmap) {
+            if (tid < BM) {
+                int4 rec{-1, 0, 0, 0};
+                if (m0 + tid < a.M) p8_row_pixel(m0 + tid, a.N, a.Ho, a.Wo, a.p8_g, rec.x, rec.y, rec.z, rec.w);
+                ((int4*)smem)[tid] = rec;
+            }
+            __syncthreads();
+            const int4 first = ((const int4*)smem)[0], last = ((const int4*)smem)[min(BM, a.M - m0) - 1];
+            int kh_hi;
+            p8_kh_range(__builtin_amdgcn_readfirstlane(first.y), __builtin_amdgcn_readfirstlane(last.y),
+                        __builtin_amdgcn_readfirstlane(first.w) == __builtin_amdgcn_readfirstlane(last.w), a.H, a.sh,
+                        a.ph, KH, kh_lo, kh_hi);
+            kt_lo = kh_lo * KW * csteps;
+            kt_hi = kh_hi * KW * csteps;
+        }
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int g = 0; g < NA; ++g) {
             const int r = g * 128 + h * 64 + wid * 8 + sub;
-            const int m = m0 + r;
-            const bool okm = m < a.M;
-            const int mm = okm ? m : 0;
-            const int n = mm / HoWo, rem = mm - n * HoWo;
-            const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
+            bool okm;
+            int n, oh, ow;
+            if (ROWS && rowmap) {
+                const int4 rec = ((const int4*)smem)[r];
+                okm = rec.x >= 0;
+                n = okm ? rec.x : 0;
+                oh = rec.y;
+                ow = rec.z;
+            } else {
+                const int m = m0 + r;
+                okm = m < a.M;
+                const int mm = okm ? m : 0;
+                n = mm / HoWo;
+                const int rem = mm - n * HoWo;
+                oh = rem / a.Wo;
+                ow = rem - oh * a.Wo;
+            }
             const int ih0 = oh * a.sh - a.ph, iw0 = ow * a.sw - a.pw;
             a2_px[h][g] = a.x2 ? (const bf16*)a.x2 + (((int64_t)n * a.H2 + oh * a.s2) * a.W2 + ow * a.s2) * cin2 +
                                      ((pch ^ ((r >> 1) & 7)) * 8)
@@ -841,8 +879,15 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
     // The A K-tiles walk (tap, channel step) in order, so the next K-tile's tap and input offset are kept as
     // scalar state advanced once per K-tile (no per-issue divisions / 64-bit products: SQ_ACTIVE_INST_SCA was
     // 10-11 % of the wave cycles with them).  nx_*: the K-tile the next A issues read.
+    // The walk starts at K-tile kt_lo = the first channel step of tap (kh_lo, 0); the weights stay indexed by kt.
     int nx_cs = 0, nx_tap = 0, nx_kh = 0, nx_kw = 0;
-    int nx_off = fold_c(0, a.xfold);   // (kh * W + kw) * xld + channel offset: < 2^31 at every shape taken
+    if constexpr (ROWS) {
+        nx_kh = kh_lo;
+        nx_tap = nx_kh * KW;
+        if (rowmap) __syncthreads();   // every row record is read before the first DMA lands on it
+    }
+    // (kh * W + kw) * xld + channel offset: < 2^31 at every shape taken
+    int nx_off = nx_kh * a.W * xld + fold_c(0, a.xfold);
     auto advance = [&]() {
         if (++nx_cs == csteps) {
             nx_cs = 0;
@@ -890,15 +935,15 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
     bf16x8 av[4][2], bv[2][2];
 
 #pragma unroll
-    for (int w = 0; w < 4; ++w) issue(0, w);
+    for (int w = 0; w < 4; ++w) issue(kt_lo, w);
     advance();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (wid >= 4) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind
-    for (int kt = 0; kt < nk; ++kt) {
+    for (int kt = kt_lo; kt < kt_hi; ++kt) {
         const char* A = smem + (kt & 1) * S::BUF;
         const char* B = A + BM * 128;
-        const bool more = kt + 1 < nk;
+        const bool more = kt + 1 < kt_hi;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int mi = q >> 1, ni = (q == 1 || q == 2) ? 1 : 0;
@@ -959,6 +1004,26 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
     const bool relu = flags & CBW_EPI_RELU;
     const bool has_res = a.res != nullptr;
     const bool res_split = flags & CBW_EPI_RES_SPLIT, res_f32 = flags & CBW_EPI_RES_F32;
+    // row order: the output pixel of each logical row, decoded once per tile into the now idle LDS (every DMA is
+    // retired and every fragment read done behind the barriers above); -1 past M
+    if constexpr (ROWS) {
+        if (rowmap) {
+            if (tid < BM) {
+                int n, oh, ow, grp, m = -1;
+                if (m0 + tid < a.M) {
+                    p8_row_pixel(m0 + tid, a.N, a.Ho, a.Wo, a.p8_g, n, oh, ow, grp);
+                    m = (n * a.Ho + oh) * a.Wo + ow;
+                }
+                ((int*)smem)[tid] = m;
+            }
+            __syncthreads();
+        }
+    }
+    // pixel of the wave's row 16 f + fr (rows past M: -1 in row order, >= M otherwise)
+    auto row_m = [&](int f) {
+        if (ROWS && rowmap) return ((const int*)smem)[wr * 128 + f * 16 + fr];
+        return m0 + wr * 128 + f * 16 + fr;
+    };
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
         const int col = n0 + ni * (BN / 2) + wc * 32 + fq * 8;
@@ -971,7 +1036,7 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
         if (has_res) {
 #pragma unroll
             for (int f = 0; f < 8; ++f) {
-                const int mc = min(m0 + wr * 128 + f * 16 + fr, a.M - 1);
+                const int mc = (ROWS && rowmap) ? max(row_m(f), 0) : min(row_m(f), a.M - 1);
                 if (res_f32) {
                     const float* rp = (const float*)a.res + (int64_t)mc * a.res_ld + col;
                     rw0[f] = *(const uint4*)rp;
@@ -985,8 +1050,8 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
         }
 #pragma unroll
         for (int f = 0; f < 8; ++f) {
-            const int m = m0 + wr * 128 + f * 16 + fr;
-            if (m >= a.M) continue;
+            const int m = row_m(f);
+            if ((ROWS && rowmap) ? m < 0 : m >= a.M) continue;
             float v[8];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -1018,9 +1083,23 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
     }
 }
 
+// CBW_P8_ROWSKIP (default 1): the 3x3 tiles in row order without their all-padding kernel rows (p8_rowmap.h); 0 = the
+// (pair, oh, ow) order and all nine taps -- the same bits, the dropped K-tiles added exact zeros.  CBW_P8_ROWGROUP = G
+// overrides the group size (0 / unset: p8_default_rowgroup; above N: one group, the flat order).  Read per launch.
+int p8_rowgroup(const ConvArgs& a, int BM) {
+    const char* e = getenv("CBW_P8_ROWSKIP");
+    if ((e && atoi(e) == 0) || a.N <= 0 || (int64_t)a.N * a.Ho * a.Wo != a.M) return 0;
+    const char* ge = getenv("CBW_P8_ROWGROUP");
+    int G = ge ? atoi(ge) : 0;
+    if (G <= 0) G = p8_default_rowgroup(a.Wo, BM);
+    return G < a.N ? G : a.N;
+}
+
 template <int KH, int KW, int BN = 256>
-hipError_t launch_p8(const ConvArgs& a, hipStream_t st) {
+hipError_t launch_p8(const ConvArgs& a0, hipStream_t st) {
     using S = P8Shape<BN>;
+    ConvArgs a = a0;
+    a.p8_g = KH * KW > 1 ? p8_rowgroup(a, S::BM) : 0;
     if (BN != 256) {   // 160 KB of dynamic LDS
         static const hipError_t attr = hipFuncSetAttribute((const void*)conv_igemm_p8<KH, KW, BN>,
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S::BUF);

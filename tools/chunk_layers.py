@@ -1,6 +1,7 @@
 """One scoring chunk's conv launches in order, with isolated durations, from a rocprofv3 --pmc pass over bench.py
 (the counter passes serialise the kernels): the launches of one queue between two stem launches, each named by its
 ResNet-50 layer (LEF maps [3, 75, 750]) and priced against max(MFMA at 1.1 PF, HBM bytes at 5.5 TB/s).
+A --pmc FETCH_SIZE pass also gets each launch's fetched bytes (fabric side: counter x2 on gfx950, KB).
 usage: [CHUNK_PAIRS=834] python tools/chunk_layers.py DIR [chunk_index]  (CHUNK_PAIRS = bench.py --chunk of the pass)"""
 import collections
 import os
@@ -17,7 +18,8 @@ for r in csv.DictReader(open(f)):
     if k not in disp:
         disp[k] = (r["Queue_Id"], re.sub(r"\(.*", "", r["Kernel_Name"].replace("(anonymous namespace)::", "")).replace("void ", "")[:44],
                    int(r["Grid_Size"]) // int(r["Workgroup_Size"]),
-                   (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+                   (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3,
+                   float(r["Counter_Value"]) * 2048 / 1e6 if r.get("Counter_Name") == "FETCH_SIZE" else None)
 byq = collections.defaultdict(list)
 for k in sorted(disp):
     byq[disp[k][0]].append(disp[k])
@@ -51,17 +53,18 @@ for q, l in byq.items():
         continue
     seq = l[st[want]:st[want + 1]] if want + 1 < len(st) else l[st[want]:]
     if os.environ.get("RAW"):   # RAW=1: the chunk's launches as recorded (any pass: the fp8 tier's chunk too)
-        for _, n, g, d in seq:
-            print(f"{n:44s} grid={g:5d} {d:7.1f}us")
+        for _, n, g, d, fb in seq:
+            print(f"{n:44s} grid={g:5d} {d:7.1f}us" + ("" if fb is None else f" fetch {fb:7.1f}MB"))
         print(f"chunk total {sum(x[3] for x in seq):.0f} us over {len(seq)} launches ({P} pairs)")
         break
     tot = totr = 0.0
-    for i, (_, n, g, d) in enumerate(seq[:len(layers)]):
+    for i, (_, n, g, d, fb) in enumerate(seq[:len(layers)]):
         M, N, K, B = sh[i]
         fl = 2.0 * M * N * K * P
         t_roof = max(fl / 1.1e15, B * P / 5.5e12) * 1e6
         tot += d
         totr += t_roof
-        print(f"{layers[i]:18s} {n:44s} grid={g:5d} {d:7.1f}us  {fl / d / 1e6:6.0f}TF/s {B * P / d / 1e6:5.2f}TB/s  roof {t_roof:6.1f}us x{d / t_roof:4.2f}")
+        print(f"{layers[i]:18s} {n:44s} grid={g:5d} {d:7.1f}us  {fl / d / 1e6:6.0f}TF/s {B * P / d / 1e6:5.2f}TB/s  roof {t_roof:6.1f}us x{d / t_roof:4.2f}"
+              + ("" if fb is None else f"  fetch {fb:7.1f}MB"))
     print(f"chunk total {tot:.0f} us, roofline {totr:.0f} us ({P} pairs: {tot / P:.2f} us per pair)")
     break
