@@ -35,6 +35,7 @@
 // value).  Tiles away from the column edges of an LEF-shaped map (H = TH) take precomputed masks;
 // the others (edge columns, other heights) compute them.
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 
 #include "cbw_common.h"
@@ -929,15 +930,11 @@ __global__ __launch_bounds__(512, 1) void bottleneck_ring_kernel(const bf16* __r
 }
 
 int num_cus_bt() {   // the persistent grid; CBW_BT_CUS=N (A/B) sizes it for N CUs, leaving the rest to the other streams
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    static const int cap = [] {
         const char* e = getenv("CBW_BT_CUS");
-        if (e && atoi(e) > 0) n = std::min(n, atoi(e));
-    }
-    return n;
+        return e && atoi(e) > 0 ? atoi(e) : INT_MAX;
+    }();
+    return std::min(cbw_num_cus(), cap);
 }
 
 template <int CIN, bool Q8 = false>

@@ -6,57 +6,19 @@
 #include <initializer_list>
 #include <string>
 
+#include "conv_args.h"
+
 typedef __bf16 bf16;
+struct ConvRoute;   // conv_route.h
 
-enum {
-    CBW_EPI_RELU = 1,
-    CBW_EPI_GELU = 2,
-    CBW_EPI_RES_F32 = 4,       // residual operand is fp32 (else bf16)
-    CBW_EPI_OUT_F32 = 8,       // output is fp32 (else bf16)
-    CBW_EPI_RES_AFTER_ACT = 16, // y = act(acc + bias) + res   (else act(acc + bias + res))
-    // compensated bf16 output (the 3-term split re-scoring tier): y is bf16 [M][2*Cout] = [hi | lo] with
-    // hi = bf16(v), lo = bf16(v - hi); a following conv reads it with xfold = Cout as the three K-segments
-    // [hi | hi | lo] against weights [w_hi | w_lo | w_hi], summing x_hi.w_hi + x_hi.w_lo + x_lo.w_hi in
-    // fp32; y32 (optional) receives v in fp32 [M][Cout].  Tile kernels only.
-    CBW_EPI_SPLIT3 = 32,
-    // residual given as such a [hi | lo] tensor (res_ld = 2*Cout): res = hi + lo
-    CBW_EPI_RES_SPLIT = 64
-};
+// compute units of the current device (cached per device; 256 if the query fails): every grid and fill rule sizes by it
+int cbw_num_cus();
 
-struct ConvArgs {
-    const void* x;      // [N][H][W][Cin] bf16
-    const void* w;      // [Cout][KH][KW][Cin] bf16
-    const float* bias;  // [Cout] or null
-    const void* res;    // [M][res_ld] or null
-    void* y;            // [M][y_ld]
-    const void* zero;   // >= 16 bytes of zeros in device memory
-    int N, H, W, Cin, Ho, Wo, Cout, KH, KW;
-    int sh, sw, ph, pw;
-    int M;              // N*Ho*Wo
-    int res_ld, y_ld;
-    int flags;
-    // optional second K-source (1x1 convs only): y = act([x | x2(strided)] . w + bias) with
-    // w [Cout][Cin + Cin2]; x2 is [N][H2][W2][Cin2] sampled at (oh*s2, ow*s2).  Used to fold a
-    // ResNet shortcut conv into the expand conv of the same block (no shortcut tensor in HBM).
-    const void* x2;
-    int Cin2, H2, W2, s2;
-    // split-K (conv_igemm_kernel only, set by cbw_conv_igemm_splitk): block z of grid.y accumulates K-steps
-    // [z nsteps / ksplit, (z + 1) nsteps / ksplit) and stores raw fp32 sums to partial[z][M][Cout]
-    int ksplit;
-    float* partial;
-    float* y32;         // CBW_EPI_SPLIT3: optional fp32 copy of the output, [M][Cout]
-    // folded input (tile kernels only): x holds x_ld channels per pixel (0 = Cin); with xfold = C > 0 the K
-    // channels [0, Cin = 3C) read physical channels c < C ? c : c - C, i.e. a [hi | lo] tensor (x_ld = 2C)
-    // seen as [hi | hi | lo]
-    int x_ld, xfold;
-    // conv_igemm_p8's 3x3 tiles (set by its launcher, see p8_rowmap.h): > 0 = tile rows in (group of p8_g pairs, oh,
-    // pair, ow) order with the all-padding kernel rows dropped from each tile's K loop; 0 = (pair, oh, ow) order
-    int p8_g;
-};
-
+// the bf16 family's dispatch: launches the route conv_route.h gives for (a, cbw_num_cus(), the CBW_* knobs read now)
 hipError_t cbw_conv_igemm(const ConvArgs& a, hipStream_t st);
 // the kernel (rocprofv3's short name, template arguments included) the last conv dispatch on this host thread
-// launched: a string literal or a per-instantiation static, so the runtime's profile records keep the pointer
+// launched: ConvRoute::name for the bf16 family, a per-instantiation static for the fp8 one, so the runtime's profile
+// records keep the pointer.  Every dispatch that returns hipSuccess has set it.
 extern thread_local const char* cbw_last_conv_kernel;
 // the CUs cbw_conv_stream sizes its persistent grid for (0: all): set by the KWS runtime while keyword chunks run on
 // several streams, so the HBM-bound streaming convs leave CUs to the other streams' MFMA-bound convs
@@ -139,18 +101,18 @@ hipError_t cbw_cvt_fp8_probe(const float* x, uint8_t* q, float* back, int n, hip
 // residual/output, ReLU or none; hipErrorNotSupported otherwise
 bool cbw_conv_ring_supported(const ConvArgs& a);
 hipError_t cbw_conv_ring(const ConvArgs& a, hipStream_t st);
+hipError_t cbw_conv_ring(const ConvArgs& a, const ConvRoute& r, hipStream_t st);   // r: conv_ring_route's / conv_route's
 // row-stationary streaming 1x1 kernel (conv_stream.hip): stride-1 1x1, K = Cin (+ Cin2) in {128, 256, 384, 512}
 // (K 512 on 16-pixel units; CBW_CS_K512=0 sends K 512 back to the tile kernels), weights stationary in LDS,
 // rows in registers; for the HBM-bound expand convs and the K 256 / 512 reduces
 bool cbw_conv_stream_supported(const ConvArgs& a);
-bool cbw_conv_stream_wanted(const ConvArgs& a);
 hipError_t cbw_conv_stream(const ConvArgs& a, hipStream_t st);
+hipError_t cbw_conv_stream(const ConvArgs& a, const ConvRoute& r, hipStream_t st);   // r: conv_stream_route's / conv_route's
 // the stage-2 identity junction in one launch (conv_stream.hip): a = the expand 128 -> 512 with its bf16 residual and
 // ReLU (y as cbw_conv_stream writes it), and t1 [M][128] = relu(y . wr^T + br), the next block's 1x1 reduce,
 // bit-identical to the two launches.  wr_packed: the reduce weights [128][512] in the kernel's fragment order
 // (cbw_conv_chain_pack, 128 KB).  red_cout: the reduce's output channels (128).  CBW_CS_CHAIN=0 disables the chain
-// per call (cbw_conv_chain_enabled); the grid obeys cbw_cs_grid_cus like cbw_conv_stream
-bool cbw_conv_chain_enabled();
+// per call; the grid obeys cbw_cs_grid_cus like cbw_conv_stream
 bool cbw_conv_chain_supported(const ConvArgs& a, int red_cout);
 hipError_t cbw_conv_chain_pack(const uint16_t* wr, uint16_t* packed, hipStream_t st);
 hipError_t cbw_conv_chain(const ConvArgs& a, const uint16_t* wr_packed, const float* br, void* t1, hipStream_t st);

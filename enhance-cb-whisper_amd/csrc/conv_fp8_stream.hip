@@ -217,16 +217,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void conv_fp8_stream_kernel(F8ConvAr
     }
 }
 
-int fs_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    }
-    return n;
-}
-
 int fs_slice(int cout, int k) {   // the largest divisor of Cout, a multiple of 64, within the LDS budget
     for (int nsl = 1; nsl <= cout / 64; ++nsl) {
         if (cout % nsl) continue;
@@ -272,7 +262,7 @@ hipError_t cbw_conv_fp8_stream(const F8ConvArgs& a, hipStream_t st) {
     if (!cbw_conv_fp8_stream_supported(a)) return hipErrorNotSupported;
     const int sn = fs_slice(a.Cout, a.Cin);
     const int nslice = a.Cout / sn;
-    const int cus = cbw_cs_grid_cus > 0 ? std::min(fs_num_cus(), cbw_cs_grid_cus) : fs_num_cus();
+    const int cus = cbw_cs_grid_cus > 0 ? std::min(cbw_num_cus(), cbw_cs_grid_cus) : cbw_num_cus();
     const int G = 8 * nslice * std::max(1, cus / (8 * nslice));
     const size_t lds = (size_t)sn * a.Cin + (size_t)sn * 8;
     switch (a.Cin) {

@@ -21,9 +21,22 @@
 // stores run on 16-byte row vectors.
 #include "cbw_common.h"
 #include "cbw_kernels.h"
-#include "p8_rowmap.h"
+#include "conv_route.h"
+
+#include <atomic>
 
 thread_local const char* cbw_last_conv_kernel = "";
+
+int cbw_num_cus() {
+    static std::atomic<int> cache[16];   // per device, 0 = not asked yet
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    const bool slot = dev >= 0 && dev < 16;
+    if (slot && (n = cache[dev].load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    if (slot) cache[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
 
 namespace {
 
@@ -729,11 +742,8 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_big2(ConvArgs a) {
 }
 
 template <int BN, int KH, int KW>
-hipError_t launch_big(const ConvArgs& a, hipStream_t st) {
-    const int nt = ((a.M + BIG_BM - 1) / BIG_BM) * (a.Cout / BN);
+hipError_t launch_big(const ConvArgs& a, int nt, hipStream_t st) {
     constexpr int lds = BIG_NS * (BIG_BM + BN) * 64;
-    static const std::string nm = kernel_name("conv_igemm_big2", {BN, KH, KW});
-    cbw_last_conv_kernel = nm.c_str();
     hipLaunchKernelGGL((conv_igemm_big2<BN, KH, KW>), dim3(nt), dim3(512), lds, st, a);
     return hipGetLastError();
 }
@@ -1083,165 +1093,53 @@ __global__ __launch_bounds__(512, 1) void conv_igemm_p8(ConvArgs a) {
     }
 }
 
-// CBW_P8_ROWSKIP (default 1): the 3x3 tiles in row order without their all-padding kernel rows (p8_rowmap.h); 0 = the
-// (pair, oh, ow) order and all nine taps -- the same bits, the dropped K-tiles added exact zeros.  CBW_P8_ROWGROUP = G
-// overrides the group size (0 / unset: p8_default_rowgroup; above N: one group, the flat order).  Read per launch.
-int p8_rowgroup(const ConvArgs& a, int BM) {
-    const char* e = getenv("CBW_P8_ROWSKIP");
-    if ((e && atoi(e) == 0) || a.N <= 0 || (int64_t)a.N * a.Ho * a.Wo != a.M) return 0;
-    const char* ge = getenv("CBW_P8_ROWGROUP");
-    int G = ge ? atoi(ge) : 0;
-    if (G <= 0) G = p8_default_rowgroup(a.Wo, BM);
-    return G < a.N ? G : a.N;
-}
+static_assert(BK == CONV_BK && P8_BK == CONV_BK && P8_BM == conv_p8_bm(P8_BN) && P8Shape<128>::BM == conv_p8_bm(128) &&
+                  BIG_BM == CONV_BIG_BM && BIG_BK == CONV_BIG_BK,
+              "conv_route.h decides for these tiles");
 
-template <int KH, int KW, int BN = 256>
-hipError_t launch_p8(const ConvArgs& a0, hipStream_t st) {
+template <int KH, int KW, int BN>
+hipError_t launch_p8(const ConvArgs& a0, const ConvRoute& r, hipStream_t st) {
     using S = P8Shape<BN>;
     ConvArgs a = a0;
-    a.p8_g = KH * KW > 1 ? p8_rowgroup(a, S::BM) : 0;
+    a.p8_g = r.p8_g;
     if (BN != 256) {   // 160 KB of dynamic LDS
         static const hipError_t attr = hipFuncSetAttribute((const void*)conv_igemm_p8<KH, KW, BN>,
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S::BUF);
         if (attr != hipSuccess) return attr;
     }
-    static const std::string nm = kernel_name("conv_igemm_p8", {KH, KW, BN});
-    cbw_last_conv_kernel = nm.c_str();
-    const int nt = ((a.M + S::BM - 1) / S::BM) * (a.Cout / BN);
-    hipLaunchKernelGGL((conv_igemm_p8<KH, KW, BN>), dim3(nt), dim3(512), 2 * S::BUF, st, a);
+    hipLaunchKernelGGL((conv_igemm_p8<KH, KW, BN>), dim3(r.tiles), dim3(512), 2 * S::BUF, st, a);
     return hipGetLastError();
 }
 
-// CBW_CONV_P8 (default 1): the 8-phase kernel for the convs conv_igemm_big2 would run (Cout % 256, Cin % 64).
-// tools/layer_bench.py, 625 LEF pairs, big2 -> p8: stage-3 reduce 136 -> 118 us, stage-4 first reduce 231 -> 185,
-// stage-3 first 3x3 230 -> 204, other 3x3s within +-1.5 %; bench.py 4.59 -> 4.72 utt/s (two rounds each)
-int p8_x2() {   // CBW_P8_X2: 0 never, 1 the x2 convs ring / persist would run, 2 also those on the streaming kernel
-    const char* e = getenv("CBW_P8_X2");
-    return e ? atoi(e) : 1;
-}
-
-bool p8_tier_enabled() {
-    const char* e = getenv("CBW_P8_TIER");
-    return !(e && atoi(e) == 0);
-}
-
-int p8_n128() {
-    const char* e = getenv("CBW_P8_N128");
-    return e ? atoi(e) : 1;
-}
-
-int p8_mode() {
-    const char* e = getenv("CBW_CONV_P8");
-    return e ? atoi(e) : 1;
-}
-
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    }
-    return n;
-}
-
 template <int BM, int BN, int KH, int KW>
-hipError_t launch_persist(const ConvArgs& a, hipStream_t st) {
-    const int ntiles = ((a.M + BM - 1) / BM) * (a.Cout / BN);
-    int G = 2 * num_cus();
-    if (ntiles < G) G = ntiles;
+hipError_t launch_persist(const ConvArgs& a, int ntiles, hipStream_t st) {
+    const int G = std::min(ntiles, 2 * cbw_num_cus());
     constexpr int lds = 2 * (BM + BN) * 128 + 4 * 8 * EPI_LD * 4;
-    static const std::string nm = kernel_name("conv_igemm_persist", {BM, BN, KH, KW});
-    cbw_last_conv_kernel = nm.c_str();
     hipLaunchKernelGGL((conv_igemm_persist<BM, BN, KH, KW>), dim3(G), dim3(256), lds, st, a, ntiles);
     return hipGetLastError();
 }
 
 template <int BM, int BN, int KH, int KW>
-hipError_t launch_t(const ConvArgs& a, hipStream_t st) {
-    const int nt = ((a.M + BM - 1) / BM) * (a.Cout / BN);
+hipError_t launch_t(const ConvArgs& a, int nt, hipStream_t st) {
     constexpr int lds = lds_bytes<BM, BN>();
-    static const std::string nm = kernel_name("conv_igemm_kernel", {BM, BN, KH, KW});
-    cbw_last_conv_kernel = nm.c_str();
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, KH, KW>), dim3(nt), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
-// The persistent ring kernel (conv_ring.hip) wins where HBM and latency bound the conv: 1x1 convs
-// with K <= 768 and no residual (tools/chunk_trace.py, chunk of 500 LEF pairs: stage-2 first-block
-// reduce 366 -> 316 us, fused expand+shortcut 424 -> 368 us).  Identity-residual expands stay on
-// conv_igemm_persist (2 blocks/CU hide the residual's HBM latency: ring 275 -> 315 us); the
-// MFMA-bound ones (3x3, K >= 1024) keep the 256x256 tiles of conv_igemm_big (half the L2 -> LDS
-// bytes per FLOP of the ring's 256x128 tile).
-bool ring_wanted(const ConvArgs& a) {
-    if (!cbw_conv_ring_supported(a)) return false;
-    const int ktot = a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
-    return a.KH * a.KW == 1 && a.res == nullptr && ktot <= 768;
-}
-
+// the route's kernel at this tap shape: each case computes only its grid and LDS
 template <int KH, int KW>
-hipError_t launch_k(const ConvArgs& a, hipStream_t st) {
-    // the tile kernels advance A through a 32-bit scalar offset (tap row/col + channel step): it must fit
-    const int64_t xld = a.x_ld ? a.x_ld : a.Cin;
-    if (((int64_t)(KH - 1) * a.W + (KW - 1)) * xld + a.Cin + (a.x2 ? a.Cin2 : 0) > INT32_MAX) return hipErrorInvalidValue;
-    const bool tile_only = a.xfold || (a.x_ld && a.x_ld != a.Cin) || (a.flags & (CBW_EPI_SPLIT3 | CBW_EPI_RES_SPLIT));
-    const bool p8_fit = p8_mode() == 1 && a.res == nullptr && a.Cout % P8_BN == 0 && a.Cin % P8_BK == 0 &&
-                        a.xfold % P8_BK == 0 && KH * KW * a.Cin + (a.x2 ? a.Cin2 : 0) >= 512 &&
-                        (a.x2 == nullptr || (KH * KW == 1 && a.Cin2 % P8_BK == 0 && !a.xfold && !a.x_ld)) &&
-                        !(a.flags & (CBW_EPI_OUT_F32 | CBW_EPI_GELU | CBW_EPI_RES_SPLIT)) &&
-                        ((a.M + P8_BM - 1) / P8_BM) * (a.Cout / P8_BN) >= num_cus();
-    // folded expand + shortcut (x2): ring / persist -> p8 (CBW_P8_X2 >= 1), streaming -> p8 (CBW_P8_X2 = 2)
-    const int px2 = p8_x2();
-    if (p8_fit && a.x2 && px2 >= 2) return launch_p8<KH, KW>(a, st);
-    if (!tile_only && KH * KW == 1 && cbw_conv_stream_wanted(a)) return cbw_conv_stream(a, st);
-    if (p8_fit && a.x2 && px2 >= 1) return launch_p8<KH, KW>(a, st);
-    // the compensated tier's convs (CBW_EPI_SPLIT3) at 256 x 256 tiles ("run the tier's stages 3-4
-    // at larger tiles"): its expand convs with the [hi | lo] / fp32 residual and its fp32-output shortcuts on p8's
-    // residual epilogue, and deep-K convs (K >= 4096: stage 4 at ~400 band pairs, 226 tiles) from half a round of
-    // tiles -- one p8 tile's long K loop outruns four 128 x 128 tiles there.  CBW_P8_TIER=0: the tile kernels.
-    if (p8_tier_enabled() && (a.flags & (CBW_EPI_SPLIT3 | CBW_EPI_OUT_F32)) && a.xfold && a.x2 == nullptr &&
-        p8_mode() == 1 && a.Cout % P8_BN == 0 && a.Cin % P8_BK == 0 && a.xfold % P8_BK == 0 &&
-        !(a.flags & (CBW_EPI_GELU | CBW_EPI_RES_AFTER_ACT))) {
-        const int ktot = KH * KW * a.Cin;
-        const int tiles = ((a.M + P8_BM - 1) / P8_BM) * (a.Cout / P8_BN);
-        if (ktot >= 512 && (tiles >= num_cus() || (ktot >= 4096 && 2 * tiles >= num_cus())))
-            return launch_p8<KH, KW>(a, st);
+hipError_t launch_k(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    switch (r.kernel) {
+        case ConvKernel::Stream: return cbw_conv_stream(a, r, st);
+        case ConvKernel::Ring: return cbw_conv_ring(a, r, st);
+        case ConvKernel::P8:
+            return r.BN == 256 ? launch_p8<KH, KW, 256>(a, r, st) : launch_p8<KH, KW, 128>(a, r, st);
+        case ConvKernel::Big2: return launch_big<256, KH, KW>(a, r.tiles, st);
+        case ConvKernel::Persist: return launch_persist<128, 128, KH, KW>(a, r.tiles, st);
+        case ConvKernel::Tile:
+            return r.BN == 128 ? launch_t<128, 128, KH, KW>(a, r.tiles, st) : launch_t<256, 64, KH, KW>(a, r.tiles, st);
+        default: return hipErrorInvalidValue;
     }
-    if (!tile_only && ring_wanted(a)) return cbw_conv_ring(a, st);
-    // MFMA-bound shapes (K >= 256, no residual, bf16 out, no second K-source) -> 8-wave ring kernel
-    // (conv_igemm_big2 also takes the compensated tier's [hi | lo] inputs and split outputs -- x_ld, xfold,
-    // CBW_EPI_SPLIT3 -- so its 3x3 and deep-K 1x1 convs run on the same kernel as the bf16 pass)
-    const bool big_ok = a.res == nullptr && a.x2 == nullptr &&
-                        !(a.flags & (CBW_EPI_OUT_F32 | CBW_EPI_GELU | CBW_EPI_RES_SPLIT)) &&
-                        a.Cin % BIG_BK == 0 && a.xfold % BIG_BK == 0 && KH * KW * a.Cin >= 256;
-    const int big_tiles = ((a.M + BIG_BM - 1) / BIG_BM) * (a.Cout / 256);
-    // (stage 4's 282 tiles fill 1.1 rounds, but the 4-wave kernel there loses more in the two-stream bench
-    // than the tail costs: 5.57 vs 5.69 utt/s)
-    if (big_ok && big_tiles >= num_cus()) {
-        // (a 128-wide tile for the few-tile stage-4 convs -- 282 tiles = 1.1 rounds at LEF -- fills the
-        // rounds better but loses more per tile: 5.18 -> 5.05 utt/s in bench.py; not taken)
-        // 256-wide tiles only: at Cout = 128 (the stage-2 3x3s) the 4-wave 128x128 kernel below is faster
-        // (tools/layer_bench.py: 184 vs 202 us stride 1, 229 vs 237 us stride 2; bench.py +0.6 %)
-        if (a.Cout % 256 == 0 && p8_mode() == 1 && a.Cin % P8_BK == 0 && a.xfold % P8_BK == 0)
-            return launch_p8<KH, KW>(a, st);
-        if (a.Cout % 256 == 0) return launch_big<256, KH, KW>(a, st);
-    }
-    // Cout 128 (the stage-2 3x3s): the 8-phase schedule on 512 x 128 tiles (CBW_P8_N128=0: the 4-wave kernel below)
-    if (big_ok && p8_n128() && p8_mode() == 1 && a.Cout % 256 == 128 && a.Cin % P8_BK == 0 && a.xfold % P8_BK == 0 &&
-        KH * KW * a.Cin >= 512 && ((a.M + 511) / 512) * (a.Cout / 128) >= num_cus())
-        return launch_p8<KH, KW, 128>(a, st);
-    // tile shape: keep BN <= Cout; prefer the 128x128 tile when it divides Cout
-    if (a.Cout % 128 == 0) {
-        // persistent cross-tile pipelining pays where the per-tile prologue/epilogue is not
-        // amortised: a single K-stage, or a residual read in the epilogue (tools/layer_bench.py:
-        // S1 expand 493 -> 404 us, S2 expand 298 -> 267 us); deep-K tiles keep the 1-tile kernel.
-        const bool short_k = a.KH * a.KW * (a.Cin / BK) == 1;
-        if (a.x2 != nullptr || short_k || a.res != nullptr)
-            return launch_persist<128, 128, KH, KW>(a, st);
-        return launch_t<128, 128, KH, KW>(a, st);
-    }
-    if (a.x2 != nullptr) return hipErrorInvalidValue;   // dual-source needs Cout % 128 == 0
-    return launch_t<256, 64, KH, KW>(a, st);
 }
 
 }  // namespace
@@ -1290,15 +1188,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(ConvArgs a, int S)
 }
 }  // namespace
 
-int cbw_conv_splitk_factor(const ConvArgs& a) {
-    if (a.KH != 1 || a.KW != 1 || a.x2 != nullptr || a.Cout % 128 || a.Cin % BK) return 1;
-    const int tiles = ((a.M + 127) / 128) * (a.Cout / 128);
-    const int slots = 2 * num_cus();               // conv_igemm_kernel: 2 blocks per CU
-    const int nsteps = a.Cin / BK;
-    int S = 1;
-    while (S < 8 && tiles * (S * 2) <= slots && nsteps / (S * 2) >= 4) S *= 2;
-    return S;
-}
+int cbw_conv_splitk_factor(const ConvArgs& a) { return conv_splitk_factor(a, cbw_num_cus()); }
 
 hipError_t cbw_conv_igemm_splitk(const ConvArgs& a0, int ksplit, float* partial, hipStream_t st) {
     if (ksplit <= 1 || partial == nullptr) return cbw_conv_igemm(a0, st);
@@ -1313,15 +1203,16 @@ hipError_t cbw_conv_igemm_splitk(const ConvArgs& a0, int ksplit, float* partial,
     cbw_last_conv_kernel = "conv_igemm_kernel<128, 128, 1, 1> + splitk_epilogue_kernel";
     hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 1, 1>), dim3(nt, ksplit), dim3(256), lds, st, a);
     const int64_t n4 = (int64_t)a.M * a.Cout / 4;
-    const int grid = (int)std::min<int64_t>((n4 + 255) / 256, 4 * num_cus());
+    const int grid = (int)std::min<int64_t>((n4 + 255) / 256, 4 * cbw_num_cus());
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(grid), dim3(256), 0, st, a, ksplit);
     return hipGetLastError();
 }
 
 hipError_t cbw_conv_igemm(const ConvArgs& a, hipStream_t st) {
-    if (a.x2 != nullptr && (a.KH != 1 || a.KW != 1 || a.Cin2 % BK)) return hipErrorInvalidValue;
-    if (a.KH == 1 && a.KW == 1) return launch_k<1, 1>(a, st);
-    if (a.KH == 3 && a.KW == 3) return launch_k<3, 3>(a, st);
-    if (a.KH == 1 && a.KW == 3) return launch_k<1, 3>(a, st);
-    return hipErrorInvalidValue;
+    const ConvRoute r = conv_route(a, cbw_num_cus(), conv_knobs_from_env());
+    if (r.kernel == ConvKernel::Invalid) return hipErrorInvalidValue;
+    cbw_last_conv_kernel = r.name;
+    if (a.KW == 1) return launch_k<1, 1>(a, r, st);   // (a route has one of these three tap shapes)
+    if (a.KH == 3) return launch_k<3, 3>(a, r, st);
+    return launch_k<1, 3>(a, r, st);
 }

@@ -22,6 +22,7 @@
 // check, so every wave issues the same number of stores and the counted waits stay exact).
 #include "cbw_common.h"
 #include "cbw_kernels.h"
+#include "conv_route.h"
 
 typedef int ring_i32x2 __attribute__((ext_vector_type(2)));
 typedef int ring_i32x4 __attribute__((ext_vector_type(4)));
@@ -261,39 +262,25 @@ __global__ __launch_bounds__(512, 1) void conv_ring_kernel(ConvArgs a, int ntile
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int ring_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    }
-    return n;
-}
+static_assert(R_BM == CONV_RING_BM && R_BN == CONV_RING_BN && R_BK == CONV_RING_BK && R_MAXC == CONV_RING_MAXC,
+              "conv_route.h decides for these tiles");
 
 template <int KH, int KW>
-hipError_t launch_ring(const ConvArgs& a, hipStream_t st) {
-    const int ntiles = ((a.M + R_BM - 1) / R_BM) * (a.Cout / R_BN);
-    const int G = std::min(ntiles, ring_cus());
-    static const std::string nm = kernel_name("conv_ring_kernel", {KH, KW});
-    cbw_last_conv_kernel = nm.c_str();
+hipError_t launch_ring(const ConvArgs& a, int ntiles, hipStream_t st) {
+    const int G = std::min(ntiles, cbw_num_cus());
     hipLaunchKernelGGL((conv_ring_kernel<KH, KW>), dim3(G), dim3(512), R_LDS, st, a, ntiles);
     return hipGetLastError();
 }
 
 }  // namespace
 
-bool cbw_conv_ring_supported(const ConvArgs& a) {
-    if (a.Cout % R_BN || a.Cout > R_MAXC || a.Cin % R_BK || a.M <= 0) return false;
-    if (a.flags & ~CBW_EPI_RELU) return false;   // bf16 output, ReLU or none
-    if (a.res) return false;                     // identity-residual expands: conv_igemm_persist
-    if (a.y_ld % 4 || (int64_t)a.M * a.y_ld * 2 >= 0x7fffffffLL) return false;
-    if (a.x2 && (a.KH * a.KW != 1 || a.Cin2 % R_BK)) return false;
-    return (a.KH == 1 && a.KW == 1) || (a.KH == 3 && a.KW == 3);
-}
+bool cbw_conv_ring_supported(const ConvArgs& a) { return conv_ring_supported(a); }
 
-hipError_t cbw_conv_ring(const ConvArgs& a, hipStream_t st) {
-    if (!cbw_conv_ring_supported(a)) return hipErrorNotSupported;
-    if (a.KH == 1) return launch_ring<1, 1>(a, st);
-    return launch_ring<3, 3>(a, st);
+hipError_t cbw_conv_ring(const ConvArgs& a, hipStream_t st) { return cbw_conv_ring(a, conv_ring_route(a), st); }
+
+hipError_t cbw_conv_ring(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    if (r.kernel != ConvKernel::Ring || !conv_ring_supported(a) || r.tiles != conv_tiles(a, R_BM, R_BN))
+        return hipErrorNotSupported;
+    if (a.KH == 1) return launch_ring<1, 1>(a, r.tiles, st);
+    return launch_ring<3, 3>(a, r.tiles, st);
 }

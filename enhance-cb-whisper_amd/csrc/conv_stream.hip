@@ -27,8 +27,11 @@
 //     row group sit on the same XCD (blockIdx % 8) and walk the same units in the same order, so the
 //     rows are fetched from HBM once and re-read from that XCD's L2.
 // MFMAs run transposed (C^T = W . X^T): the pixel sits on the lane (fr), the channel on the register.
+#include <climits>
+
 #include "cbw_common.h"
 #include "cbw_kernels.h"
+#include "conv_route.h"
 
 typedef int cs_i32x4 __attribute__((ext_vector_type(4)));
 // raw buffer load / store (LLVM intrinsics by asm label): 32-bit offsets against one descriptor; the
@@ -388,16 +391,17 @@ __global__ void conv_chain_pack_kernel(const bf16* __restrict__ w, bf16* __restr
     *(bf16x8*)(out + (int64_t)e * 8) = *(const bf16x8*)(w + (int64_t)perm_row(16 * c + fr) * CC_N + kk * 32 + fq * 8);
 }
 
-int num_cus_cs() {   // the persistent grid; CBW_CS_CUS=N (A/B) sizes it for N CUs, leaving the rest to the other streams
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+static_assert(CS_WBYTES == CONV_CS_WBYTES && CS_MAXSLICE == CONV_CS_MAXSLICE, "conv_route.h slices for this LDS budget");
+static_assert(CC_K == CONV_CC_K && CC_N == CONV_CC_N && CC_R == CONV_CC_R, "conv_route.h chains these shapes");
+
+// the persistent grid: CBW_CS_CUS=N (A/B) sizes it for N CUs, cbw_cs_grid_cus for what the runtime leaves this stream
+int cs_grid_cus() {
+    static const int cap = [] {
         const char* e = getenv("CBW_CS_CUS");
-        if (e && atoi(e) > 0) n = std::min(n, atoi(e));
-    }
-    return n;
+        return e && atoi(e) > 0 ? atoi(e) : INT_MAX;
+    }();
+    const int n = std::min(cbw_num_cus(), cap);
+    return cbw_cs_grid_cus > 0 ? std::min(n, cbw_cs_grid_cus) : n;
 }
 
 int cs_exp() {   // CBW_CS_EXP diagnostic builds: 1 no residual loads, 2 no stores (wrong results)
@@ -405,111 +409,45 @@ int cs_exp() {   // CBW_CS_EXP diagnostic builds: 1 no residual loads, 2 no stor
     return e ? atoi(e) : 0;
 }
 
-int stream_prefetch() {   // CBW_CS_PREFETCH: -1 policy (default), 0 off, 1 on wherever it fits the registers
-    const char* e = getenv("CBW_CS_PREFETCH");
-    return e ? atoi(e) : -1;
-}
-
-// K 512 on the streaming kernel (16-pixel units, 8 waves; CBW_CS_K512=0 keeps the tile kernels).
-// tools/layer_bench.py, LEF chunk of 500: stage-2 reduce 512 -> 128 140.7 -> 120.5 us, stage-3 first
-// reduce 512 -> 256 227.0 -> 183.9 us, stage-4 identity expand 512 -> 2048 + res 163.4 -> 120.7 us
-int stream_k512() {
-    const char* e = getenv("CBW_CS_K512");
-    return e ? atoi(e) : 1;
-}
-
-int stream_mode() {   // CBW_CONV_STREAM=0 keeps these convs on the tile kernels (A/B experiments)
-    const char* e = getenv("CBW_CONV_STREAM");
-    return e ? atoi(e) : 1;
-}
-
-// the weight slice: the largest divisor of Cout that is a multiple of 128 channels and fits the budget
-int slice_channels(int cout, int ktot) {
-    for (int nsl = 1; nsl <= cout / 128; ++nsl) {
-        if (cout % nsl) continue;
-        const int sn = cout / nsl;
-        if (sn % 128 == 0 && sn <= CS_MAXSLICE && (int64_t)sn * ktot * 2 <= CS_WBYTES) return sn;
-    }
-    return 0;
-}
-
 }  // namespace
 
 thread_local int cbw_cs_grid_cus = 0;
 
-bool cbw_conv_stream_supported(const ConvArgs& a) {
-    const int ktot = a.Cin + (a.x2 ? a.Cin2 : 0);
-    if (a.KH != 1 || a.KW != 1 || a.sh != 1 || a.sw != 1 || a.ph != 0 || a.pw != 0) return false;
-    if (ktot != 128 && ktot != 256 && ktot != 384 && !(ktot == 512 && stream_k512())) return false;
-    if (a.Cin % 32 || (a.x2 && a.Cin2 % 32)) return false;
-    if (a.flags & ~CBW_EPI_RELU) return false;                   // bf16 residual / output, ReLU or none
-    if (a.res && a.res_ld % 4) return false;
-    if (a.y_ld % 4 || a.M <= 0) return false;
-    const int64_t lim = 0x7ffffff0LL - 4096;   // 32-bit buffer offsets, out-of-range marker above
-    if ((int64_t)a.M * a.y_ld * 2 >= lim || (int64_t)a.M * a.Cin * 2 >= lim) return false;
-    if (a.res && (int64_t)a.M * a.res_ld * 2 >= lim) return false;
-    if (a.x2 && (int64_t)a.N * a.H2 * a.W2 * a.Cin2 * 2 >= lim) return false;
-    return slice_channels(a.Cout, ktot) > 0;
-}
-
-// policy: every supported conv -- at LEF sizes the identity expands (stage 2: 274 -> 244 us, stage 3: 182 ->
-// 137 us), the folded-shortcut expands of stages 1-2 and the stage-2 first reduce (307 -> 284 us)
-bool cbw_conv_stream_wanted(const ConvArgs& a) {
-    return stream_mode() != 0 && cbw_conv_stream_supported(a);
-}
+bool cbw_conv_stream_supported(const ConvArgs& a) { return conv_stream_supported(a, conv_knobs_from_env()); }
 
 hipError_t cbw_conv_stream(const ConvArgs& a, hipStream_t st) {
-    if (!cbw_conv_stream_supported(a)) return hipErrorNotSupported;
+    return cbw_conv_stream(a, conv_stream_route(a, conv_knobs_from_env()), st);
+}
+
+hipError_t cbw_conv_stream(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    // (the guard is the kernel's own: what it can run whatever the knobs prefer)
     const int ktot = a.Cin + (a.x2 ? a.Cin2 : 0);
+    if (r.kernel != ConvKernel::Stream || !conv_stream_supported(a, ConvKnobs{}) || r.stream.ks * 32 != ktot)
+        return hipErrorNotSupported;
     const int sn = slice_channels(a.Cout, ktot);
     const int nslice = a.Cout / sn;
-    const int cus = cbw_cs_grid_cus > 0 ? std::min(num_cus_cs(), cbw_cs_grid_cus) : num_cus_cs();
-    const int G = 8 * nslice * std::max(1, cus / (8 * nslice));
+    const int G = 8 * nslice * std::max(1, cs_grid_cus() / (8 * nslice));
     const size_t lds = (size_t)sn * ktot * 2 + (size_t)sn * 4;
-    // (tools/layer_bench.py, LEF chunk of 500: K 128 -- 12 waves, 2 residual steps in flight 244 us vs
-    // 16 waves, 1 step 256 us; K 256 -- 12 waves, 1 step 137 us vs 8 waves, 2 steps 143 us; 16-pixel units
-    // with 16 waves: within 2 % at K 128, 6 % slower at K 256)
-    // next-unit row prefetch (tools/layer_bench.py, LEF chunk of 500, LB_VAR=CBW_CS_PREFETCH): K 128 on 8 waves
-    // 243.6 -> 237.6 us (stage-2 expand); K 256 on 8 waves 283.9 -> 273.5 us without a residual (stage-2 first
-    // reduce) but 136.7 -> 142.5 us with one (stage-3 expand: the 12-wave residual latency hiding wins)
-    const int pf = stream_prefetch();
-    const int pn = pf >= 0 ? pf : (ktot == 128 || (ktot == 256 && !a.res));
-#define CS_LAUNCH(KS, WAVES, RD, PFD, PN)                                                                               \
-    do {                                                                                                           \
-        cbw_last_conv_kernel = "conv_stream_kernel<" #KS ", " #WAVES ", " #RD ", " #PFD ", " #PN ">";                \
-        hipLaunchKernelGGL((conv_stream_kernel<KS, WAVES, RD, PFD, PN>), dim3(G), dim3(WAVES * 64), lds, st, a,       \
-                           nslice, sn, cs_exp());                                                                  \
-    } while (0)
-    switch (ktot) {
-        case 128:
-            if (pn) CS_LAUNCH(4, 8, 2, 2, 1);
-            else CS_LAUNCH(4, 12, 2, 2, 0);
-            break;
-        case 256:
-            if (pn) CS_LAUNCH(8, 8, 1, 2, 1);
-            else CS_LAUNCH(8, 12, 1, 2, 0);
-            break;
-        case 512:
-            CS_LAUNCH(16, 8, 2, 1, 0);
-            break;
-        default:   // (K 384 with the prefetch: 244 VGPRs spilled)
-            CS_LAUNCH(12, 8, 2, 2, 0);
-            break;
+    const ConvStreamVariant& v = r.stream;
+#define CS_LAUNCH(KS, WAVES, RD, PFD, PN)                                                                         \
+    if (v.ks == KS && v.waves == WAVES && v.rd == RD && v.pfd == PFD && v.pn == PN) {                             \
+        hipLaunchKernelGGL((conv_stream_kernel<KS, WAVES, RD, PFD, PN>), dim3(G), dim3(WAVES * 64), lds, st, a, \
+                           nslice, sn, cs_exp());                                                                \
+        return hipGetLastError();                                                                                \
     }
+    CS_LAUNCH(4, 8, 2, 2, 1)
+    CS_LAUNCH(4, 12, 2, 2, 0)
+    CS_LAUNCH(8, 8, 1, 2, 1)
+    CS_LAUNCH(8, 12, 1, 2, 0)
+    CS_LAUNCH(16, 8, 2, 1, 0)
+    CS_LAUNCH(12, 8, 2, 2, 0)
 #undef CS_LAUNCH
-    return hipGetLastError();
+    return hipErrorInvalidValue;   // a variant conv_route.h names and this file does not instantiate
 }
 
 // ---- chained expand + next reduce (conv_stream_chain_kernel)
-bool cbw_conv_chain_enabled() {   // CBW_CS_CHAIN=0 keeps the two launches; read on every call (tests A/B in one process)
-    const char* e = getenv("CBW_CS_CHAIN");
-    return !e || atoi(e) != 0;
-}
-
 bool cbw_conv_chain_supported(const ConvArgs& a, int red_cout) {
-    if (!cbw_conv_stream_supported(a) || a.x2 || a.Cin != CC_K || a.Cout != CC_N || red_cout != CC_R) return false;
-    if (!a.res || a.flags != CBW_EPI_RELU || a.y_ld != CC_N) return false;
-    return slice_channels(a.Cout, a.Cin) == a.Cout;   // one weight slice
+    return conv_chain_supported(a, red_cout, conv_knobs_from_env());
 }
 
 hipError_t cbw_conv_chain_pack(const uint16_t* wr, uint16_t* packed, hipStream_t st) {
@@ -519,14 +457,11 @@ hipError_t cbw_conv_chain_pack(const uint16_t* wr, uint16_t* packed, hipStream_t
 }
 
 hipError_t cbw_conv_chain(const ConvArgs& a, const uint16_t* wr_packed, const float* br, void* t1, hipStream_t st) {
-    if (!cbw_conv_chain_supported(a, CC_R) || !wr_packed || !t1) return hipErrorNotSupported;
-    const int cus = cbw_cs_grid_cus > 0 ? std::min(num_cus_cs(), cbw_cs_grid_cus) : num_cus_cs();
-    const int G = 8 * std::max(1, cus / 8);
+    const ConvRoute r = conv_chain_route(a, CC_R, conv_knobs_from_env());
+    if (r.kernel != ConvKernel::Chain || !wr_packed || !t1) return hipErrorNotSupported;
+    const int G = 8 * std::max(1, cs_grid_cus() / 8);
     const size_t lds = (size_t)CC_N * CC_K * 2 + (size_t)(CC_N + CC_R) * 4;
-    // 4 waves x 64-pixel units, 2 residual steps in flight (isolated, 834 LEF pairs, whole grid: 448-465 us against
-    // 365 + 214 us for the two launches; 8 waves x 32-pixel units read Wr twice as often: 565-588 us, and 516 us
-    // with 2 residual steps in flight, which spills; Wr row-major instead of fragment order: 750 us)
-    cbw_last_conv_kernel = "conv_stream_chain_kernel<4, 2, 4>";
+    cbw_last_conv_kernel = r.name;
     hipLaunchKernelGGL((conv_stream_chain_kernel<4, 2, 4>), dim3(G), dim3(4 * 64), lds, st, a, (const bf16*)wr_packed, br,
                        t1);
     return hipGetLastError();

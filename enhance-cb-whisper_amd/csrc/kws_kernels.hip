@@ -1315,10 +1315,7 @@ hipError_t cbw_stem_pool(const uint16_t* x, const uint16_t* w, const float* bias
     const int nct = (Wp + SP_PW - 1) / SP_PW;
     const int64_t nt = (int64_t)N * nrt * nct;
     if (nt >= (1LL << 31)) return hipErrorInvalidValue;
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    const int64_t G = std::min<int64_t>(nt, 2 * (int64_t)ncu);
+    const int64_t G = std::min<int64_t>(nt, 2 * (int64_t)cbw_num_cus());
     const char* v1 = getenv("CBW_STEM_V1");   // A/B: the round-4 epilogue and pool (read per call)
     // round 6's V3 (default on full-height tiles; CBW_STEM_V3=0: V2): tools/stem_bench.py, 625 LEF pairs, alternating
     // runs 361.9 / 367.5 vs 373.2 / 377.3 us, bit-identical
@@ -1343,10 +1340,7 @@ hipError_t cbw_stem16_pool(const uint16_t* x, const uint16_t* w, const float* bi
     const int nct = (Wp + SP_PW - 1) / SP_PW;
     const int64_t nt = (int64_t)N * nrt * nct;
     if (nt >= (1LL << 31)) return hipErrorInvalidValue;
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    const int64_t G = std::min<int64_t>(nt, ncu);
+    const int64_t G = std::min<int64_t>(nt, cbw_num_cus());
     hipLaunchKernelGGL(stem16_pool_kernel<false>, dim3((unsigned)G), dim3(256), s16_lds_bytes(R), st, (const bf16*)x,
                        (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nrt, nct);
     return hipGetLastError();
@@ -1360,10 +1354,7 @@ hipError_t cbw_stem16_pool_x3(const uint16_t* x, const uint16_t* w, const float*
     const int nct = (Wp + SP_PW - 1) / SP_PW;
     const int64_t nt = (int64_t)N * nrt * nct;
     if (nt >= (1LL << 31)) return hipErrorInvalidValue;
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    const int64_t G = std::min<int64_t>(nt, ncu);
+    const int64_t G = std::min<int64_t>(nt, cbw_num_cus());
     hipLaunchKernelGGL(stem16_pool_kernel<true>, dim3((unsigned)G), dim3(256), s16_lds_bytes(R, true), st,
                        (const bf16*)x, (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nrt, nct);
     return hipGetLastError();

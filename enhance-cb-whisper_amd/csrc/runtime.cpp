@@ -16,6 +16,7 @@
 
 #include "cbw.h"
 #include "cbw_kernels.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -263,7 +264,6 @@ int launch_conv(const ConvW& c, const void* x, int N, int H, int W, void* y, con
     a.flags = flags | (c.relu ? CBW_EPI_RELU : 0);
     int slot;
     CHK(Prof::begin(prof, st, &slot));
-    cbw_last_conv_kernel = "?";
     if (splitk_ws) HIPCHK(cbw_conv_igemm_splitk(a, cbw_conv_splitk_factor(a), splitk_ws, st));
     else HIPCHK(cbw_conv_igemm(a, st));
     return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * ((double)a.Cin * a.KH * a.KW + (a.x2 ? a.Cin2 : 0)),
@@ -276,23 +276,19 @@ int launch_conv(const ConvW& c, const void* x, int N, int H, int W, void* y, con
 int launch_chain(const ConvW& c2, const ConvW& r0, const DevBuf& r0_packed, const void* t2, int N, int H, int W, void* y,
                  const void* res, void* t1n, const void* zero, hipStream_t st, Prof* prof, bool* done) {
     *done = false;
-    if (!r0_packed.p || !res || !cbw_conv_chain_enabled()) return CBW_OK;
-    if (c2.k != 1 || c2.stride != 1 || c2.relu || r0.k != 1 || r0.stride != 1 || !r0.relu || r0.cin != c2.cout)
-        return CBW_OK;
-    ConvArgs a{};
+    if (!r0_packed.p || !res || c2.relu) return CBW_OK;   // (the block's ReLU follows the residual add)
+    ConvArgs a{}, r{};   // the two convs as their own launches would see them
     a.x = t2; a.w = c2.w.p; a.bias = c2.b.as<float>(); a.res = res; a.y = y; a.zero = zero;
-    a.N = N; a.H = a.Ho = H; a.W = a.Wo = W; a.Cin = c2.cin; a.Cout = c2.cout; a.KH = a.KW = 1;
-    a.sh = a.sw = 1;
-    a.M = N * H * W;
+    conv_geometry(a, c2, N, H, W);
     a.res_ld = a.y_ld = c2.cout;
     a.flags = CBW_EPI_RELU;
-    ConvArgs r = a;   // the reduce as its own launch would see it
-    r.x = y; r.w = r0.w.p; r.bias = r0.b.as<float>(); r.res = nullptr; r.y = t1n;
-    r.Cin = r0.cin; r.Cout = r0.cout; r.res_ld = r.y_ld = r0.cout;
-    if (!cbw_conv_stream_wanted(a) || !cbw_conv_stream_wanted(r) || !cbw_conv_chain_supported(a, r0.cout)) return CBW_OK;
+    r.x = y; r.w = r0.w.p; r.bias = r0.b.as<float>(); r.y = t1n; r.zero = zero;
+    conv_geometry(r, r0, N, a.Ho, a.Wo);
+    r.res_ld = r.y_ld = r0.cout;
+    r.flags = r0.relu ? CBW_EPI_RELU : 0;
+    if (conv_junction_route(a, r, conv_knobs_from_env()).kernel != ConvKernel::Chain) return CBW_OK;
     int slot;
     CHK(Prof::begin(prof, st, &slot));
-    cbw_last_conv_kernel = "?";
     HIPCHK(cbw_conv_chain(a, r0_packed.as<uint16_t>(), r0.b.as<float>(), t1n, st));
     CHK(Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin + 2.0 * a.M * r0.cout * (double)r0.cin,
                   cbw_last_conv_kernel));
@@ -433,7 +429,6 @@ int launch_conv_x3(const ConvShape& c, const void* w, const float* bias, const v
     a.flags = flags | (res ? (res_split ? CBW_EPI_RES_SPLIT : CBW_EPI_RES_F32) : 0) | (c.relu ? CBW_EPI_RELU : 0);
     int slot;
     CHK(Prof::begin(prof, st, &slot));
-    cbw_last_conv_kernel = "?";
     HIPCHK(cbw_conv_igemm(a, st));
     // the compensated conv's GEMM: K over the three split segments; always tier 1
     return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel, 1);
@@ -780,7 +775,6 @@ int launch_conv_f8(const cbw_kws* h, const ConvF8& c, const uint8_t* x, int N, i
     if (!cbw_conv_fp8_supported(a)) return fail(CBW_ERR_INVALID, "fp8 conv shape not supported");
     int slot;
     CHK(Prof::begin(prof, st, &slot));
-    cbw_last_conv_kernel = "?";
     HIPCHK(cbw_conv_fp8(a, st));
     return Prof::end(prof, slot, st, 2.0 * a.M * a.Cout * (double)a.Cin * a.KH * a.KW, cbw_last_conv_kernel);
 }
@@ -949,10 +943,7 @@ namespace {
 int cs_shared_cus() {
     const char* e = getenv("CBW_CS_SHARED_CUS");
     if (e) return atoi(e);
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n * 3 / 8;
+    return cbw_num_cus() * 3 / 8;
 }
 struct ChunkStreams {
     cbw_kws* h;
