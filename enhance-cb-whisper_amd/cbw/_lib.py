@@ -79,6 +79,18 @@ SIGNATURES = {
     "cbw_kws_score_resized_workspace_bytes": (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     "cbw_kws_score_resized": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "cbw_kws_score_resized_batch_workspace_bytes": (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                              c_int]),
+    "cbw_kws_score_resized_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                            c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "cbw_kws_sim_rows_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                      c_int, c_int, c_void_p, c_void_p]),
+    "cbw_kws_rescore_resized_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                              c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_int64, c_void_p]),
+    "cbw_kws_rescore_resized_x3_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                 c_int64, c_void_p]),
     "cbw_kws_build_exact": (c_int, [c_void_p]),
     "cbw_kws_rescore_resized_workspace_bytes": (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "cbw_kws_rescore_resized": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,

@@ -752,6 +752,110 @@ class KwsEngine:
         stats["fp32"] = n2
         return logits, stats
 
+    def score_resized_batch(self, utt_hs: torch.Tensor, kwd_hs, out_size: Tuple[int, int] = (150, 750),
+                            chunk: Optional[int] = None) -> torch.Tensor:
+        """``score_resized`` for a batch of segments in one pass (cbw_kws_score_resized_batch; cb_whisper.py:87-129,
+        where keyword_spotting scores every segment against every keyword): utt_hs [B, L, Tu, D] -> logits f32
+        [B, K, 2].  Row b carries the bits ``score_resized(utt_hs[b], ...)`` gives, whatever ``chunk`` (which counts
+        (segment, keyword) pairs here) and whatever else the batch holds."""
+        if self.variant != VARIANT_L:
+            raise ValueError("score_resized_batch takes raw hs: build the engine with learn_features=False")
+        rows, off = kwd_hs if isinstance(kwd_hs, tuple) else pack_keywords(kwd_hs, self.device)
+        rows = rows.to(self.device, torch.bfloat16).contiguous()
+        off_host = off.to("cpu", torch.int32).contiguous()
+        off_dev = off_host.to(self.device)
+        utt = utt_hs.to(self.device, torch.bfloat16).contiguous()
+        if utt.dim() != 4:
+            raise ValueError(f"score_resized_batch takes utt_hs [B, L, Tu, D], got {tuple(utt.shape)}")
+        B, L, Tu, D = utt.shape
+        if L != self.n_layers or rows.shape[0] != L or rows.shape[2] != D:
+            raise ValueError(f"shape mismatch: utt {tuple(utt.shape)} keyword rows {tuple(rows.shape)}")
+        K = off_host.numel() - 1
+        Ho, Wo = out_size
+        chunk = chunk or self.default_chunk(Ho, Wo, budget_bytes=1 << 30)
+        logits = torch.empty((B, K, 2), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            nb = self.lib.cbw_kws_score_resized_batch_workspace_bytes(self.h, off_host.data_ptr(), K, B, Tu, D, Ho, Wo,
+                                                                      chunk)
+            if nb < 0:
+                _lib.check(-1, "cbw_kws_score_resized_batch_workspace_bytes")
+            ws = self._ws.get(nb, self.device)
+            _lib.check(self.lib.cbw_kws_score_resized_batch(self.h, utt.data_ptr(), B, Tu, rows.data_ptr(),
+                                                            rows.shape[1], D, off_dev.data_ptr(), off_host.data_ptr(),
+                                                            K, Ho, Wo, logits.data_ptr(), chunk, ws.data_ptr(),
+                                                            ws.numel(), _lib.stream_handle()),
+                       "cbw_kws_score_resized_batch")
+        return logits
+
+    def rescore_resized_batch(self, utt32: torch.Tensor, kwd32_packed, out_size: Tuple[int, int], logits: torch.Tensor,
+                              sel: torch.Tensor, tier: str = "f32", trusted: bool = False) -> torch.Tensor:
+        """``rescore_resized`` for a batch of segments (cbw_kws_rescore_resized_batch / _x3_batch): utt32 f32
+        [B, L, Tu, D]; ``sel`` indexes the B * K pairs p = b * K + k, the rows of ``logits`` [B, K, 2], which are
+        rewritten in place, every other row untouched.  A pair's logits carry the bits ``rescore_resized`` gives for
+        that utterance and keyword."""
+        if tier not in ("f32", "x3"):
+            raise ValueError(f"unknown re-scoring tier {tier}")
+        if not self.has_exact_resized:
+            raise _lib.CbwError("rescore_resized_batch needs the fp32 networks: call KwsEngine.build_exact() first")
+        rows, off_host, off_dev, K = self._packed_f32(kwd32_packed)
+        utt = utt32.to(self.device).contiguous()
+        if utt.dim() != 4:
+            raise ValueError(f"rescore_resized_batch takes utt32 [B, L, Tu, D], got {tuple(utt.shape)}")
+        B, L, Tu, D = utt.shape
+        if utt.dtype != torch.float32 or L != self.n_layers or rows.shape[2] != D:
+            raise ValueError(f"shape mismatch: utt {tuple(utt.shape)} {utt.dtype} keyword rows {tuple(rows.shape)}")
+        if (tuple(logits.shape) != (B, K, 2) or logits.dtype != torch.float32 or not logits.is_contiguous()
+                or logits.device != self.device):
+            raise ValueError(f"rescore_resized_batch: logits must be contiguous f32 [{B}, {K}, 2] on {self.device}, "
+                             f"got {tuple(logits.shape)} {logits.dtype}")
+        sel = self._pair_index(sel, B * K, trusted, "sel")
+        n = sel.numel()
+        if n == 0:
+            return logits
+        Ho, Wo = out_size
+        wsq, call = ((self.lib.cbw_kws_rescore_resized_workspace_bytes, self.lib.cbw_kws_rescore_resized_batch)
+                     if tier == "f32" else
+                     (self.lib.cbw_kws_rescore_resized_x3_workspace_bytes, self.lib.cbw_kws_rescore_resized_x3_batch))
+        with torch.cuda.device(self.device):
+            nb = wsq(self.h, off_host.data_ptr(), K, Tu, D, Ho, Wo)   # a pass's size does not depend on B
+            if nb < 0:
+                raise ValueError(f"cbw_kws_rescore_resized_batch ({tier}) workspace: bad arguments "
+                                 f"(K {K}, Tu {Tu}, D {D}, out {Ho} x {Wo})")
+            ws = self._ws_rescore.get(nb, self.device)
+            _lib.check(call(self.h, utt.data_ptr(), B, Tu, rows.data_ptr(), rows.shape[1], D, off_dev.data_ptr(),
+                            off_host.data_ptr(), K, Ho, Wo, sel.data_ptr(), n, logits.data_ptr(), ws.data_ptr(),
+                            ws.numel(), _lib.stream_handle()), f"cbw_kws_rescore_resized_batch ({tier})")
+        return logits
+
+    def score_resized_batch_exact(self, utt_hs: torch.Tensor, kwd_packed_bf16, kwd_packed_f32,
+                                  out_size: Tuple[int, int] = (150, 750), band: float = 0.0,
+                                  band_x3: Optional[float] = 1e-4, chunk: Optional[int] = None):
+        """``score_resized_exact`` for a batch of segments utt_hs [B, L, Tu, D]: one bf16 pass
+        (``score_resized_batch``), one band selection over the B * K rows and one re-scoring call per tier for the
+        whole batch.  Returns (logits f32 [B, K, 2], stats): row b is what ``score_resized_exact`` gives for
+        utterance b, the stats are the sums over b."""
+        logits = self.score_resized_batch(utt_hs, kwd_packed_bf16, out_size, chunk=chunk)
+        B, K = logits.shape[0], logits.shape[1]
+        stats = {"band": 0, "fp32": 0, "bf16": B * K}
+        if band <= 0 or B * K == 0:
+            return logits, stats
+        flat = logits.view(B * K, 2)
+        sel, n = self.band(flat, 0.5, band)
+        stats["band"] = n
+        if n == 0:
+            return logits, stats
+        utt32 = utt_hs.to(self.device, torch.float32)
+        if band_x3 is None:
+            self.rescore_resized_batch(utt32, kwd_packed_f32, out_size, logits, sel, trusted=True)
+            stats["fp32"] = n
+            return logits, stats
+        self.rescore_resized_batch(utt32, kwd_packed_f32, out_size, logits, sel, tier="x3", trusted=True)
+        sel2, n2 = self.band(flat, 0.5, band_x3)
+        if n2:
+            self.rescore_resized_batch(utt32, kwd_packed_f32, out_size, logits, sel2, trusted=True)
+        stats["fp32"] = n2
+        return logits, stats
+
     # ------------------------------------------------------------------ decision
     def spot(self, logits: torch.Tensor, ghost: Optional[torch.Tensor] = None, threshold: float = 0.5,
              mode: str = "threshold") -> Tuple[torch.Tensor, torch.Tensor]:

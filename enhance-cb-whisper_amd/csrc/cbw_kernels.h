@@ -179,6 +179,17 @@ hipError_t cbw_maps_split16(const float* x, uint16_t* y, int K, int L, int H, in
 // [off[k0+k], off[k0+k+1]) relative to off[k0]
 hipError_t cbw_sim_resize(const float* sim, int64_t layer_stride, int ld, const int* off_dev, int k0, int K, int L,
                           int Tu, int Ho, int Wo, uint16_t* out, hipStream_t st);
+// the similarity rows of pairs [p0, p0 + pc) of a batch (pair p = b * K + k) for all L layers in one launch:
+// utt bf16 [B][L][Tu][D], kwd bf16 [L][R][D] with keyword k on rows off[k] .. off[k+1]-1 (device int32 [K + 1]);
+// rows f32 [L][chunk rows][ld], the chunk's keywords' frames in pair order, row t < Tk_k column u < Tu written.
+// max_run_rows bounds the rows of one run (a keyword range of one utterance; R always does), rows_cap the chunk's
+// rows: no row at or past it is written.  D % 64 == 0; bf16 MFMA, k placed as conv_igemm_kernel places it.
+hipError_t cbw_sim_rows_bf16(const uint16_t* utt, const uint16_t* kwd, const int* off, int B, int K, int R, int L,
+                             int Tu, int D, int p0, int pc, int max_run_rows, int64_t rows_cap, int ld, float* rows,
+                             hipStream_t st);
+// cbw_sim_resize over those rows: item i = pair p0 + i -> NHWC16 bf16 out [pc][Ho][Wo][16], in pair order
+hipError_t cbw_sim_resize_batch(const float* rows, int ld, const int* off, int p0, int pc, int K, int R, int64_t rows_cap,
+                                int L, int Tu, int Ho, int Wo, uint16_t* out, hipStream_t st);
 hipError_t cbw_nchw_to_nhwc16(const float* x, uint16_t* y, int K, int L, int H, int W, hipStream_t st);
 // MaxPool2d(3,2,1) NHWC bf16, C % 8 == 0
 hipError_t cbw_maxpool3s2(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, int Ho, int Wo, hipStream_t st);
@@ -211,15 +222,16 @@ hipError_t cbw_sim_f32(const float* kwd, const float* kwd_mask, const float* utt
 hipError_t cbw_sim_f32_pairs(const float* kwd, const float* kwd_mask, int K, const float* utt, const float* utt_mask,
                              int B, const int32_t* pair_utt, const int32_t* pair_kwd, int n_pairs, const int* sel, int p0,
                              int P, float* out, int L, int Tk, int Tu, int E, hipStream_t st);
-// CB-Whisper's own spotter in fp32: utt f32 [L][Tu][D], kwd f32 [L][R][D] with keyword k on rows off[k] .. off[k+1]-1
+// CB-Whisper's own spotter in fp32: utt f32 [B][L][Tu][D], kwd f32 [L][R][D] with keyword k on rows off[k] .. off[k+1]-1
 // (device int32 [K + 1]); map p of the pass = keyword sel[p0 + p] (clamped into [0, K), its rows into [0, R) and
 // its length to TkMax in the kernel).  rows f32 [P][L][TkMax][ld] (ld >= Tu): row t < Tk_k, column u < Tu written.
-// D % 16 == 0; fp32-input MFMA, k ascending.
-hipError_t cbw_sim_rows_f32(const float* utt, const float* kwd, const int* off, const int* sel, int p0, int P, int K,
-                            int R, int L, int Tu, int D, int TkMax, int ld, float* rows, hipStream_t st);
+// D % 16 == 0; fp32-input MFMA, k ascending.  B = 1: one utterance, the kernels as they always ran; B > 1: sel indexes
+// the B * K pairs s = b * K + k (clamped into range) and the _batch kernels resolve utterance s / K, keyword s % K.
+hipError_t cbw_sim_rows_f32(const float* utt, int B, const float* kwd, const int* off, const int* sel, int p0, int P,
+                            int K, int R, int L, int Tu, int D, int TkMax, int ld, float* rows, hipStream_t st);
 // those rows resized bilinearly (cbw_sim_resize's arithmetic) to fp32 NHWC out [P][Ho][Wo][L]
-hipError_t cbw_sim_resize_f32(const float* rows, const int* off, const int* sel, int p0, int P, int K, int R, int L,
-                              int Tu, int TkMax, int ld, int Ho, int Wo, float* out, hipStream_t st);
+hipError_t cbw_sim_resize_f32(const float* rows, int B, const int* off, const int* sel, int p0, int P, int K, int R,
+                              int L, int Tu, int TkMax, int ld, int Ho, int Wo, float* out, hipStream_t st);
 hipError_t cbw_maxpool_f32(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, hipStream_t st);
 hipError_t cbw_pool_fc_f32(const float* x, const float* w, const float* b, const int* sel, int p0, int P, float* logits,
                            int HW, int C, hipStream_t st);

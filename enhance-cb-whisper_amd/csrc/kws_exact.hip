@@ -301,22 +301,30 @@ __global__ __launch_bounds__(256) void sim_f32_e64_pairs_kernel(const float* __r
 // device knows, so both kernels resolve it themselves.  k is clamped into [0, K), its first row into [0, R) and its
 // length into [0, min(R - row, TkMax)] before any address is formed: a bad index or offset gives a wrong map, never
 // an out-of-range access.
-CBW_DEV void keyword_of_sel(const int* __restrict__ off, const int* __restrict__ sel, int i, int K, int R, int TkMax,
-                            int& row0, int& Tk) {
-    const int k = min(max(sel[i], 0), K - 1);
+CBW_DEV void keyword_rows(const int* __restrict__ off, int k, int R, int TkMax, int& row0, int& Tk) {
     row0 = min(max(off[k], 0), R - 1);
     Tk = min(max(off[k + 1] - off[k], 0), min(R - row0, TkMax));
+}
+CBW_DEV void keyword_of_sel(const int* __restrict__ off, const int* __restrict__ sel, int i, int K, int R, int TkMax,
+                            int& row0, int& Tk) {
+    keyword_rows(off, min(max(sel[i], 0), K - 1), R, TkMax, row0, Tk);
+}
+// the same for a batch of B utterances (cb_whisper.py:87-129): sel[i] = pair s = b * K + k, clamped into [0, B * K)
+CBW_DEV void pair_rows_of_sel(const int* __restrict__ off, const int* __restrict__ sel, int i, int B, int K, int R,
+                              int TkMax, int& b, int& row0, int& Tk) {
+    const int s = min(max(sel[i], 0), B * K - 1);
+    b = s / K;
+    keyword_rows(off, s - b * K, R, TkMax, row0, Tk);
 }
 
 // similarity rows (cb_whisper.py:196, matmul(kwd_hs, utt_hs^T) per layer): rows f32 [P][L][TkMax][ld], map p layer l
 // row t < Tk_k column u < Tu = kwd[l][off_k + t] . utt[l][u].  One 64 x 64 tile of one (map, layer) per block on the
 // fp32-input MFMA as conv_f32_kernel runs it: exact products, fp32 accumulation, k ascending; tile rows past Tk_k
 // and columns past Tu are loaded as zeros and not stored.  Grid (row tiles of TkMax x column tiles, L, P): a block
-// whose row tile lies beyond its keyword leaves before the first barrier.  D % 16 == 0.
-__global__ __launch_bounds__(256) void sim_rows_f32_kernel(const float* __restrict__ utt, const float* __restrict__ kwd,
-                                                           const int* __restrict__ off, const int* __restrict__ sel,
-                                                           int p0, int K, int R, int Tu, int D, int TkMax, int ld,
-                                                           float* __restrict__ rows) {
+// whose row tile lies beyond its keyword leaves before the first barrier.  D % 16 == 0.  The body takes the map's
+// utterance (utt f32 [L][Tu][D]) and its keyword's rows; the kernels below resolve them.
+CBW_DEV void sim_rows_f32_body(const float* __restrict__ utt, const float* __restrict__ kwd, int row0, int Tk, int R,
+                               int Tu, int D, int TkMax, int ld, float* __restrict__ rows) {
     __shared__ float As[2][F_BK][F_BM + F_PAD];
     __shared__ float Bs[2][F_BK][F_BN + F_PAD];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -324,8 +332,6 @@ __global__ __launch_bounds__(256) void sim_rows_f32_kernel(const float* __restri
     const int nt_n = (Tu + F_BN - 1) / F_BN;
     const int m0 = (blockIdx.x / nt_n) * F_BM, n0 = (blockIdx.x % nt_n) * F_BN;
     const int l = blockIdx.y, p = blockIdx.z, L = gridDim.y;
-    int row0, Tk;
-    keyword_of_sel(off, sel, p0 + p, K, R, TkMax, row0, Tk);
     if (m0 >= Tk) return;   // uniform over the block
     const int nk = D / F_BK;
     const int lr = tid >> 2, kq = (tid & 3) * 4;
@@ -390,6 +396,27 @@ __global__ __launch_bounds__(256) void sim_rows_f32_kernel(const float* __restri
         }
 }
 
+__global__ __launch_bounds__(256) void sim_rows_f32_kernel(const float* __restrict__ utt, const float* __restrict__ kwd,
+                                                           const int* __restrict__ off, const int* __restrict__ sel,
+                                                           int p0, int K, int R, int Tu, int D, int TkMax, int ld,
+                                                           float* __restrict__ rows) {
+    int row0, Tk;
+    keyword_of_sel(off, sel, p0 + (int)blockIdx.z, K, R, TkMax, row0, Tk);
+    sim_rows_f32_body(utt, kwd, row0, Tk, R, Tu, D, TkMax, ld, rows);
+}
+
+// map p = pair sel[p0 + p] of B utterances x K keywords: utt f32 [B][L][Tu][D]
+__global__ __launch_bounds__(256) void sim_rows_f32_batch_kernel(const float* __restrict__ utt,
+                                                                 const float* __restrict__ kwd,
+                                                                 const int* __restrict__ off,
+                                                                 const int* __restrict__ sel, int p0, int B, int K, int R,
+                                                                 int Tu, int D, int TkMax, int ld,
+                                                                 float* __restrict__ rows) {
+    int b, row0, Tk;
+    pair_rows_of_sel(off, sel, p0 + (int)blockIdx.z, B, K, R, TkMax, b, row0, Tk);
+    sim_rows_f32_body(utt + (int64_t)b * gridDim.y * Tu * D, kwd, row0, Tk, R, Tu, D, TkMax, ld, rows);
+}
+
 // source coordinate of output index dst: max(scale (dst + 0.5) - 0.5, 0) with the product and the difference rounded
 // one by one (no FMA contraction), as the float64 checker's fp32 coordinates are.  Near frame 1500 one ulp of the
 // coordinate is 1.2e-4 of a frame, which an fp32 map resolves (sim_resize_kernel's bf16 output does not).
@@ -402,10 +429,12 @@ CBW_DEV float resize_src(float scale, int dst) {
 // bilinear resize of those rows to fp32 NHWC [P][Ho][Wo][L] (cb_whisper.py:206), the arithmetic of
 // kws_kernels.hip's sim_resize_kernel: PyTorch upsample_bilinear2d, align_corners=False, no antialias, scale =
 // in / out in fp32, src = max(scale (dst + 0.5) - 0.5, 0) (resize_src: rounded step by step), the neighbour clamped
-// to the last row / column.  One thread per output pixel writes its L channels.
-__global__ void sim_resize_f32_kernel(const float* __restrict__ rows, const int* __restrict__ off,
-                                      const int* __restrict__ sel, int p0, int P, int K, int R, int L, int Tu, int TkMax,
-                                      int ld, int Ho, int Wo, float* __restrict__ out) {
+// to the last row / column.  One thread per output pixel writes its L channels.  B == 1: map p = keyword sel[p0 + p];
+// B > 1 (sim_resize_f32_batch_kernel): pair sel[p0 + p] of the B * K, whose keyword alone matters here.
+template <bool BATCH>
+CBW_DEV void sim_resize_f32_body(const float* __restrict__ rows, const int* __restrict__ off,
+                                 const int* __restrict__ sel, int p0, int P, int B, int K, int R, int L, int Tu,
+                                 int TkMax, int ld, int Ho, int Wo, float* __restrict__ out) {
     const int64_t total = (int64_t)P * Ho * Wo;
     const float sx = (float)Tu / (float)Wo;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -413,8 +442,9 @@ __global__ void sim_resize_f32_kernel(const float* __restrict__ rows, const int*
         const int64_t r = i / Wo;
         const int ii = (int)(r % Ho);
         const int p = (int)(r / Ho);
-        int row0, Tk;
-        keyword_of_sel(off, sel, p0 + p, K, R, TkMax, row0, Tk);
+        int b, row0, Tk;
+        if (BATCH) pair_rows_of_sel(off, sel, p0 + p, B, K, R, TkMax, b, row0, Tk);
+        else keyword_of_sel(off, sel, p0 + p, K, R, TkMax, row0, Tk);
         float* o = out + i * L;
         if (Tk < 1) {   // no frames (refused on the host): a zero map, no read
             for (int l = 0; l < L; ++l) o[l] = 0.f;
@@ -431,6 +461,18 @@ __global__ void sim_resize_f32_kernel(const float* __restrict__ rows, const int*
                    ly1 * (lx0 * s[(int64_t)y1 * ld + x0] + lx1 * s[(int64_t)y1 * ld + x1]);
         }
     }
+}
+
+__global__ void sim_resize_f32_kernel(const float* __restrict__ rows, const int* __restrict__ off,
+                                      const int* __restrict__ sel, int p0, int P, int K, int R, int L, int Tu, int TkMax,
+                                      int ld, int Ho, int Wo, float* __restrict__ out) {
+    sim_resize_f32_body<false>(rows, off, sel, p0, P, 1, K, R, L, Tu, TkMax, ld, Ho, Wo, out);
+}
+
+__global__ void sim_resize_f32_batch_kernel(const float* __restrict__ rows, const int* __restrict__ off,
+                                            const int* __restrict__ sel, int p0, int P, int B, int K, int R, int L,
+                                            int Tu, int TkMax, int ld, int Ho, int Wo, float* __restrict__ out) {
+    sim_resize_f32_body<true>(rows, off, sel, p0, P, B, K, R, L, Tu, TkMax, ld, Ho, Wo, out);
 }
 
 __global__ void maxpool_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C,
@@ -603,24 +645,33 @@ hipError_t cbw_sim_f32_pairs(const float* kwd, const float* kwd_mask, int K, con
     return hipGetLastError();
 }
 
-hipError_t cbw_sim_rows_f32(const float* utt, const float* kwd, const int* off, const int* sel, int p0, int P, int K,
-                            int R, int L, int Tu, int D, int TkMax, int ld, float* rows, hipStream_t st) {
+hipError_t cbw_sim_rows_f32(const float* utt, int B, const float* kwd, const int* off, const int* sel, int p0, int P,
+                            int K, int R, int L, int Tu, int D, int TkMax, int ld, float* rows, hipStream_t st) {
     if (P <= 0 || P > 65535 || K < 1 || R < 1 || L < 1 || L > 65535 || Tu < 1 || D < F_BK || D % F_BK || TkMax < 1 ||
-        ld < Tu || p0 < 0)
+        ld < Tu || p0 < 0 || B < 1 || (int64_t)B * K > INT32_MAX)
         return hipErrorInvalidValue;
     const int tiles = ((TkMax + F_BM - 1) / F_BM) * ((Tu + F_BN - 1) / F_BN);
-    hipLaunchKernelGGL(sim_rows_f32_kernel, dim3(tiles, L, P), dim3(256), 0, st, utt, kwd, off, sel, p0, K, R, Tu, D,
-                       TkMax, ld, rows);
+    if (B == 1)   // one utterance: the launch it always was
+        hipLaunchKernelGGL(sim_rows_f32_kernel, dim3(tiles, L, P), dim3(256), 0, st, utt, kwd, off, sel, p0, K, R, Tu, D,
+                           TkMax, ld, rows);
+    else
+        hipLaunchKernelGGL(sim_rows_f32_batch_kernel, dim3(tiles, L, P), dim3(256), 0, st, utt, kwd, off, sel, p0, B, K,
+                           R, Tu, D, TkMax, ld, rows);
     return hipGetLastError();
 }
 
-hipError_t cbw_sim_resize_f32(const float* rows, const int* off, const int* sel, int p0, int P, int K, int R, int L,
-                              int Tu, int TkMax, int ld, int Ho, int Wo, float* out, hipStream_t st) {
-    if (P <= 0 || K < 1 || R < 1 || L < 1 || Tu < 1 || TkMax < 1 || ld < Tu || Ho < 1 || Wo < 1 || p0 < 0)
+hipError_t cbw_sim_resize_f32(const float* rows, int B, const int* off, const int* sel, int p0, int P, int K, int R,
+                              int L, int Tu, int TkMax, int ld, int Ho, int Wo, float* out, hipStream_t st) {
+    if (P <= 0 || K < 1 || R < 1 || L < 1 || Tu < 1 || TkMax < 1 || ld < Tu || Ho < 1 || Wo < 1 || p0 < 0 || B < 1 ||
+        (int64_t)B * K > INT32_MAX)
         return hipErrorInvalidValue;
     const int grid = (int)std::min<int64_t>(((int64_t)P * Ho * Wo + 255) / 256, 1 << 20);
-    hipLaunchKernelGGL(sim_resize_f32_kernel, dim3(grid), dim3(256), 0, st, rows, off, sel, p0, P, K, R, L, Tu, TkMax,
-                       ld, Ho, Wo, out);
+    if (B == 1)
+        hipLaunchKernelGGL(sim_resize_f32_kernel, dim3(grid), dim3(256), 0, st, rows, off, sel, p0, P, K, R, L, Tu,
+                           TkMax, ld, Ho, Wo, out);
+    else
+        hipLaunchKernelGGL(sim_resize_f32_batch_kernel, dim3(grid), dim3(256), 0, st, rows, off, sel, p0, P, B, K, R, L,
+                           Tu, TkMax, ld, Ho, Wo, out);
     return hipGetLastError();
 }
 

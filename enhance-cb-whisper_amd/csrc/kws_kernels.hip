@@ -1007,6 +1007,30 @@ __global__ __launch_bounds__(256, 1) void stem16_pool_kernel(const bf16* __restr
 // (Ho, Wo) by torchvision resize(antialias=False) = bilinear, align_corners=False (PyTorch
 // upsample_bilinear2d: scale = in/out, src = max(scale (dst + 0.5) - 0.5, 0), neighbour
 // clamped to the last row/column).  Output NHWC16 bf16 [K][Ho][Wo][16], channels >= L zero.
+// sim_resize_px: output pixel (ii, j) of the map whose Tk rows start at row row0 of every layer, written to o[16].
+CBW_DEV void sim_resize_px(const float* __restrict__ sim, int64_t layer_stride, int ld, int row0, int Tk, int ii, int j,
+                           float sx, int L, int Tu, int Ho, bf16* __restrict__ o) {
+    const float sy = (float)Tk / (float)Ho;
+    const float fy = fmaxf(sy * (ii + 0.5f) - 0.5f, 0.f);
+    const float fx = fmaxf(sx * (j + 0.5f) - 0.5f, 0.f);
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < Tk - 1 ? 1 : 0), x1 = x0 + (x0 < Tu - 1 ? 1 : 0);
+    const float ly1 = fy - y0, ly0 = 1.f - ly1, lx1 = fx - x0, lx0 = 1.f - lx1;
+    bf16x8 o0, o1;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+        float v = 0.f;
+        if (l < L) {
+            const float* s = sim + l * layer_stride + (int64_t)row0 * ld;
+            v = ly0 * (lx0 * s[(int64_t)y0 * ld + x0] + lx1 * s[(int64_t)y0 * ld + x1]) +
+                ly1 * (lx0 * s[(int64_t)y1 * ld + x0] + lx1 * s[(int64_t)y1 * ld + x1]);
+        }
+        if (l < 8) o0[l] = f2bf(v); else o1[l - 8] = f2bf(v);
+    }
+    *(bf16x8*)o = o0;
+    *(bf16x8*)(o + 8) = o1;
+}
+
 __global__ void sim_resize_kernel(const float* __restrict__ sim, int64_t layer_stride, int ld,
                                   const int* __restrict__ off, int k0, int K, int L, int Tu, int Ho, int Wo,
                                   bf16* __restrict__ out) {
@@ -1019,25 +1043,209 @@ __global__ void sim_resize_kernel(const float* __restrict__ sim, int64_t layer_s
         const int k = (int)(r / Ho);
         const int row0 = off[k0 + k] - off[k0];
         const int Tk = off[k0 + k + 1] - off[k0 + k];
-        const float sy = (float)Tk / (float)Ho;
-        const float fy = fmaxf(sy * (ii + 0.5f) - 0.5f, 0.f);
-        const float fx = fmaxf(sx * (j + 0.5f) - 0.5f, 0.f);
-        const int y0 = (int)fy, x0 = (int)fx;
-        const int y1 = y0 + (y0 < Tk - 1 ? 1 : 0), x1 = x0 + (x0 < Tu - 1 ? 1 : 0);
-        const float ly1 = fy - y0, ly0 = 1.f - ly1, lx1 = fx - x0, lx0 = 1.f - lx1;
-        bf16x8 o0, o1;
+        sim_resize_px(sim, layer_stride, ld, row0, Tk, ii, j, sx, L, Tu, Ho, out + i * 16);
+    }
+}
+
+// ---------------------------------------------------------------- CB-Whisper similarity rows, batched
+// A chunk of a batch is pairs [p0, p0 + pc) of the B * K pairs p = b * K + k (cb_whisper.py:87-129: every segment
+// against every keyword).  The keywords are packed one after another, so the chunk's similarity rows are at most
+// ceil(pc / K) + 1 runs, run j a contiguous keyword range [kf, kl) of utterance p0 / K + j: the first run starts at
+// keyword p0 % K, the last ends at the chunk's last pair, the ones between take all K keywords.  Everything a block
+// needs follows from (p0, pc, K, off[]) by scalar arithmetic.  Offsets are clamped into [0, R] as they are read, so
+// a bad offset array gives wrong maps, never an address out of range.
+struct SimRun {
+    int b;          // the run's utterance
+    int a_row;      // its first keyword row, in [0, R]
+    int rows;       // its rows, a_row + rows <= R
+    int64_t c_row;  // its first row among the chunk's rows
+    int64_t c_rows; // the chunk's rows (the layer pitch of the rows scratch, in rows)
+};
+CBW_DEV int off_at(const int* __restrict__ off, int k, int R) { return min(max(off[k], 0), R); }
+// the row of pair p's first frame when every pair's frames are laid one after another in pair order
+CBW_DEV int64_t pair_row(const int* __restrict__ off, int p, int K, int R, int o0, int rk) {
+    const int b = p / K, k = p - b * K;
+    return (int64_t)b * rk + max(off_at(off, k, R) - o0, 0);
+}
+CBW_DEV SimRun sim_run(const int* __restrict__ off, int p0, int pc, int K, int R, int j) {
+    SimRun r;
+    const int o0 = off_at(off, 0, R), rk = max(off_at(off, K, R) - o0, 0);
+    const int b0 = p0 / K;
+    r.b = b0 + j;
+    const int kf = j == 0 ? p0 - b0 * K : 0;
+    const int kl = min(K, p0 + pc - r.b * K);
+    r.a_row = off_at(off, kf, R);
+    r.rows = max(off_at(off, max(kl, kf), R) - r.a_row, 0);
+    const int64_t g0 = pair_row(off, p0, K, R, o0, rk);
+    r.c_row = pair_row(off, r.b * K + kf, K, R, o0, rk) - g0;
+    r.c_rows = pair_row(off, p0 + pc, K, R, o0, rk) - g0;
+    return r;
+}
+
+// sim_rows_bf16_kernel: the bf16 counterpart of kws_exact.hip's sim_rows_f32_kernel, one launch for a chunk's rows of
+// all L layers (cb_whisper.py:196, matmul(kwd_hs, utt_hs^T) per layer).  A = keyword rows bf16 [L][R][D], B =
+// utterance frames bf16 read from utt[b][l] ([B][L][Tu][D]), C = rows f32 [L][chunk rows][ld].  Grid (row tiles x
+// column tiles of a run, L, runs): a block whose row tile lies past its run leaves before the first barrier, and a
+// tile never straddles two runs.  128 x 128 x 64 tiles, 4 waves of 64 x 64 (4 x 4 MFMA 16x16x32 bf16, fp32
+// accumulation, one chain per output, k ascending); LDS is conv_igemm_kernel's image -- rows of 128 bytes, the
+// 16-byte chunk c of row r at chunk c ^ swz(r) -- read by its fragment loop, so element k of a 32-wide step sits in
+// the same lane group and slot and a row's sums carry the same bits.  Tiles go through registers (the next stage's
+// loads are in flight during the MFMAs): rows past the run and columns u >= Tu are written to LDS as zeros and never
+// stored.  The epilogue passes each wave's 64 x 64 through LDS so that rows leave as 32-byte vectors.
+constexpr int SR_BM = 128, SR_BN = 128, SR_BK = 64;
+constexpr int SR_STAGE = (SR_BM + SR_BN) * SR_BK * 2;   // 32768 bytes
+constexpr int SR_EPI_LD = 68;
+constexpr int SR_LDS = 4 * 64 * SR_EPI_LD * 4;          // 69632 >= 2 * SR_STAGE
+static_assert(SR_LDS >= 2 * SR_STAGE, "the epilogue image covers both stages");
+CBW_DEV int sr_swz(int r) { return (r >> 1) & 7; }
+
+__global__ __launch_bounds__(256, 2) void sim_rows_bf16_kernel(const bf16* __restrict__ utt, const bf16* __restrict__ kwd,
+                                                               const int* __restrict__ off, int p0, int pc, int K, int R,
+                                                               int Tu, int D, int64_t rows_cap, int ld,
+                                                               float* __restrict__ rows) {
+    __shared__ __attribute__((aligned(16))) char smem[SR_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    const int nt_n = (Tu + SR_BN - 1) / SR_BN;
+    const int m0 = ((int)blockIdx.x / nt_n) * SR_BM, n0 = ((int)blockIdx.x % nt_n) * SR_BN;
+    const int l = blockIdx.y, L = gridDim.y;
+    const SimRun run = sim_run(off, p0, pc, K, R, (int)blockIdx.z);
+    if (m0 >= run.rows) return;   // uniform over the block
+    const int64_t c_rows = min(run.c_rows, rows_cap);
+
+    // loads: thread -> 16-byte chunk (tid & 7) of rows (tid >> 3) + 32 j, j < 4, of A and of B
+    const int chunk = tid & 7, lr = tid >> 3;
+    const bf16* ap[4];
+    const bf16* bp[4];
+    bool a_ok[4], b_ok[4];
 #pragma unroll
-        for (int l = 0; l < 16; ++l) {
-            float v = 0.f;
-            if (l < L) {
-                const float* s = sim + l * layer_stride + (int64_t)row0 * ld;
-                v = ly0 * (lx0 * s[(int64_t)y0 * ld + x0] + lx1 * s[(int64_t)y0 * ld + x1]) +
-                    ly1 * (lx0 * s[(int64_t)y1 * ld + x0] + lx1 * s[(int64_t)y1 * ld + x1]);
-            }
-            if (l < 8) o0[l] = f2bf(v); else o1[l - 8] = f2bf(v);
+    for (int j = 0; j < 4; ++j) {
+        const int r = lr + 32 * j;
+        a_ok[j] = m0 + r < run.rows;
+        b_ok[j] = n0 + r < Tu;
+        ap[j] = kwd + ((int64_t)l * R + (a_ok[j] ? run.a_row + m0 + r : 0)) * D + chunk * 8;
+        bp[j] = utt + (((int64_t)run.b * L + l) * Tu + (b_ok[j] ? n0 + r : 0)) * D + chunk * 8;
+    }
+    uint4 ra[4], rb[4];
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ra[j] = a_ok[j] ? *(const uint4*)(ap[j] + kt * SR_BK) : uint4{0u, 0u, 0u, 0u};
+            rb[j] = b_ok[j] ? *(const uint4*)(bp[j] + kt * SR_BK) : uint4{0u, 0u, 0u, 0u};
         }
-        *(bf16x8*)(out + i * 16) = o0;
-        *(bf16x8*)(out + i * 16 + 8) = o1;
+    };
+    auto store = [&](int buf) {
+        char* A = smem + buf * SR_STAGE;
+        char* B = A + SR_BM * 128;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = lr + 32 * j;
+            const int o = r * 128 + ((chunk ^ sr_swz(r)) * 16);
+            *(uint4*)(A + o) = ra[j];
+            *(uint4*)(B + o) = rb[j];
+        }
+    };
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = D / SR_BK;
+    load(0);
+    store(0);
+    __syncthreads();
+    const int fr = lane & 15, fq = lane >> 4;
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) load(kt + 1);
+        const char* A = smem + buf * SR_STAGE;
+        const char* B = A + SR_BM * 128;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int g = ks * 4 + fq;
+            bf16x8 av[4], bv[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = wm * 64 + i * 16 + fr;
+                av[i] = *(const bf16x8*)(A + r * 128 + ((g ^ sr_swz(r)) * 16));
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int r = wn * 64 + j * 16 + fr;
+                bv[j] = *(const bf16x8*)(B + r * 128 + ((g ^ sr_swz(r)) * 16));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if (kt + 1 < nk) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // epilogue: wave-private fp32 image [64][SR_EPI_LD]; every wave is past the last barrier, so the stages are free
+    float* E = (float*)smem + wid * 64 * SR_EPI_LD;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) E[(i * 16 + fq * 4 + q) * SR_EPI_LD + j * 16 + fr] = acc[i][j][q];
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): own wave's LDS writes landed
+    __builtin_amdgcn_wave_barrier();
+    const int ecg = lane & 7, erow = lane >> 3;
+    const int col = n0 + wn * 64 + ecg * 8;
+    float* out = rows + (int64_t)l * c_rows * ld;
+    const bool vec = (ld & 3) == 0 && ((uintptr_t)rows & 15) == 0 && col + 8 <= Tu;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int r = it * 8 + erow;
+        const int m = m0 + wm * 64 + r;
+        const int64_t cr = run.c_row + m;
+        if (m >= run.rows || cr >= c_rows) continue;
+        const f32x4 e0 = *(const f32x4*)(E + r * SR_EPI_LD + ecg * 8);
+        const f32x4 e1 = *(const f32x4*)(E + r * SR_EPI_LD + ecg * 8 + 4);
+        float* yp = out + cr * ld + col;
+        if (vec) {
+            *(f32x4*)yp = e0;
+            *(f32x4*)(yp + 4) = e1;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (col + q < Tu) yp[q] = e0[q];
+                if (col + 4 + q < Tu) yp[4 + q] = e1[q];
+            }
+        }
+    }
+}
+
+// the batch wrapper over sim_resize_px: item i of the chunk is pair p0 + i, its rows where sim_rows_bf16_kernel put
+// them (sim f32 [L][chunk rows][ld]); maps NHWC16 bf16 [pc][Ho][Wo][16] in pair order
+__global__ void sim_resize_batch_kernel(const float* __restrict__ sim, int ld, const int* __restrict__ off, int p0,
+                                        int pc, int K, int R, int64_t rows_cap, int L, int Tu, int Ho, int Wo,
+                                        bf16* __restrict__ out) {
+    const int64_t total = (int64_t)pc * Ho * Wo;
+    const float sx = (float)Tu / (float)Wo;
+    const int o0 = off_at(off, 0, R), rk = max(off_at(off, K, R) - o0, 0);
+    const int64_t g0 = pair_row(off, p0, K, R, o0, rk);
+    const int64_t c_rows = min(pair_row(off, p0 + pc, K, R, o0, rk) - g0, rows_cap);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int j = (int)(i % Wo);
+        const int64_t r = i / Wo;
+        const int ii = (int)(r % Ho);
+        const int p = p0 + (int)(r / Ho);
+        const int k = p % K;
+        const int64_t row0 = pair_row(off, p, K, R, o0, rk) - g0;
+        const int Tk = (int)min((int64_t)max(off_at(off, k + 1, R) - off_at(off, k, R), 0), c_rows - row0);
+        if (Tk < 1) {   // no frames (refused on the host): a zero map, no read
+            *(uint4*)(out + i * 16) = uint4{0u, 0u, 0u, 0u};
+            *(uint4*)(out + i * 16 + 8) = uint4{0u, 0u, 0u, 0u};
+            continue;
+        }
+        sim_resize_px(sim, c_rows * ld, ld, (int)row0, Tk, ii, j, sx, L, Tu, Ho, out + i * 16);
     }
 }
 
@@ -1398,6 +1606,29 @@ hipError_t cbw_sim_resize(const float* sim, int64_t layer_stride, int ld, const 
     if (L > 16 || K <= 0) return K == 0 ? hipSuccess : hipErrorInvalidValue;
     hipLaunchKernelGGL(sim_resize_kernel, dim3(grid_for((int64_t)K * Ho * Wo, 256)), dim3(256), 0, st, sim,
                        layer_stride, ld, off_dev, k0, K, L, Tu, Ho, Wo, (bf16*)out);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sim_rows_bf16(const uint16_t* utt, const uint16_t* kwd, const int* off, int B, int K, int R, int L,
+                             int Tu, int D, int p0, int pc, int max_run_rows, int64_t rows_cap, int ld, float* rows,
+                             hipStream_t st) {
+    if (B < 1 || K < 1 || R < 1 || L < 1 || L > 65535 || Tu < 1 || D < SR_BK || D % SR_BK || p0 < 0 || pc < 1 ||
+        (int64_t)p0 + pc > (int64_t)B * K || (int64_t)B * K > INT32_MAX || max_run_rows < 1 || rows_cap < 1 || ld < Tu)
+        return hipErrorInvalidValue;
+    const int runs = (p0 + pc - 1) / K - p0 / K + 1;
+    const int64_t tiles = (int64_t)((std::min(max_run_rows, R) + SR_BM - 1) / SR_BM) * ((Tu + SR_BN - 1) / SR_BN);
+    if (runs > 65535 || tiles > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sim_rows_bf16_kernel, dim3((unsigned)tiles, L, runs), dim3(256), 0, st, (const bf16*)utt,
+                       (const bf16*)kwd, off, p0, pc, K, R, Tu, D, rows_cap, ld, rows);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sim_resize_batch(const float* rows, int ld, const int* off, int p0, int pc, int K, int R, int64_t rows_cap,
+                                int L, int Tu, int Ho, int Wo, uint16_t* out, hipStream_t st) {
+    if (L > 16 || L < 1 || K < 1 || R < 1 || p0 < 0 || pc < 1 || rows_cap < 1 || rows_cap > INT32_MAX || ld < Tu)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sim_resize_batch_kernel, dim3(grid_for((int64_t)pc * Ho * Wo, 256)), dim3(256), 0, st, rows, ld,
+                       off, p0, pc, K, R, rows_cap, L, Tu, Ho, Wo, (bf16*)out);
     return hipGetLastError();
 }
 

@@ -1386,6 +1386,103 @@ int cbw_kws_score_resized(cbw_kws* h, const uint16_t* utt, int Tu, const uint16_
     return CBW_OK;
 }
 
+// ---- the same spotter for a batch of segments (cb_whisper.py:87-129): pair p = b * K + k, chunks of pairs
+namespace {
+struct ResizedBatchWs {
+    int TuP = 0;
+    int64_t rmax = 0, sim_bytes = 0, chunk_bytes = 0;
+};
+// the row of pair p's first frame with every pair's frames laid one after another in pair order
+int64_t pair_row(const int32_t* off_host, int K, int64_t p) {
+    const int64_t b = p / K, k = p - b * K;
+    return b * ((int64_t)off_host[K] - off_host[0]) + (off_host[k] - off_host[0]);
+}
+// the rows of the longest run (a keyword range of one utterance) of pairs [p0, p0 + pc)
+int max_run_rows(const int32_t* off_host, int K, int64_t p0, int pc) {
+    int best = 0;
+    for (int64_t p = p0; p < p0 + pc;) {
+        const int kf = (int)(p % K), kl = (int)std::min<int64_t>(K, kf + (p0 + pc - p));
+        best = std::max(best, off_host[kl] - off_host[kf]);
+        p += kl - kf;
+    }
+    return best;
+}
+int resized_batch_ws(const cbw_kws* h, const int32_t* off_host, int K, int B, int Tu, int D, int Ho, int Wo, int chunk,
+                     ResizedBatchWs& r) {
+    if (!off_host || K < 0 || B < 1 || Tu <= 0 || D <= 0 || Ho < 7 || Wo < 7 || chunk <= 0 ||
+        (int64_t)B * K > INT32_MAX)
+        return fail(CBW_ERR_INVALID, "bad arguments");
+    for (int k = 0; k < K; ++k)
+        if (off_host[k + 1] <= off_host[k]) return fail(CBW_ERR_INVALID, "every keyword needs >= 1 frame");
+    const int64_t P = (int64_t)B * K;
+    r.TuP = (Tu + 127) / 128 * 128;
+    r.rmax = 0;
+    for (int64_t p0 = 0; p0 < P; p0 += chunk) {   // the rows scratch: the largest pair chunk's
+        const int64_t p1 = std::min<int64_t>(p0 + chunk, P);
+        r.rmax = std::max(r.rmax, pair_row(off_host, K, p1) - pair_row(off_host, K, p0));
+    }
+    if (r.rmax > INT32_MAX) return fail(CBW_ERR_INVALID, "a chunk's similarity rows exceed 2^31: use a smaller chunk");
+    r.sim_bytes = (int64_t)align_up((size_t)h->cfg.n_layers * std::max<int64_t>(r.rmax, 1) * r.TuP * 4);
+    r.chunk_bytes = chunk_ws_bytes(h, Ho, Wo, chunk);
+    return CBW_OK;
+}
+}  // namespace
+
+int64_t cbw_kws_score_resized_batch_workspace_bytes(cbw_kws* h, const int32_t* off_host, int K, int B, int Tu, int D,
+                                                    int Ho, int Wo, int chunk) {
+    if (!h || !h->finalized) return -1;
+    ResizedBatchWs r;
+    if (resized_batch_ws(h, off_host, K, B, Tu, D, Ho, Wo, chunk, r) != CBW_OK) return -1;
+    return r.sim_bytes + r.chunk_bytes;
+}
+
+int cbw_kws_score_resized_batch(cbw_kws* h, const uint16_t* utt, int B, int Tu, const uint16_t* kwd, int R, int D,
+                                const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, float* logits,
+                                int chunk, void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    if (!h || !utt || (K > 0 && (!kwd || !off_dev || !off_host || !logits))) return fail(CBW_ERR_INVALID, "null argument");
+    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
+    if (h->cfg.variant != 0) return fail(CBW_ERR_INVALID, "the resized-similarity path takes raw hs (variant 0)");
+    if (B < 1) return fail(CBW_ERR_INVALID, "B must be >= 1");
+    if (K == 0) return CBW_OK;
+    if (D % 64) return fail(CBW_ERR_INVALID, "D must be a multiple of 64");
+    ResizedBatchWs r;
+    CHK(resized_batch_ws(h, off_host, K, B, Tu, D, Ho, Wo, chunk, r));
+    if (off_host[0] < 0 || off_host[K] > R) return fail(CBW_ERR_INVALID, "keyword rows out of range");
+    if ((uintptr_t)utt % 16 || (uintptr_t)kwd % 16) return fail(CBW_ERR_INVALID, "utt and kwd must be 16-byte aligned");
+    if (ws_bytes < r.sim_bytes + r.chunk_bytes) return fail(CBW_ERR_OOM, "workspace too small");
+    if (!ws) return fail(CBW_ERR_INVALID, "null workspace");
+    hipStream_t st = (hipStream_t)stream;
+    const int L = h->cfg.n_layers;
+    float* sims = (float*)ws;
+    char* cws = (char*)ws + r.sim_bytes;
+    const KwsPlan plan = kws_plan(h, Ho, Wo, chunk);
+    const int64_t P = (int64_t)B * K;
+    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
+        const int pc = (int)std::min<int64_t>(chunk, P - p0);
+        const int64_t rows = pair_row(off_host, K, p0 + pc) - pair_row(off_host, K, p0);
+        // sim[l] = kwd[l] . utt[b][l]^T for the chunk's runs (cb_whisper.py:196, inputs normalised), all layers at once
+        HIPCHK(cbw_sim_rows_bf16(utt, kwd, off_dev, B, K, R, L, Tu, D, (int)p0, pc, max_run_rows(off_host, K, p0, pc),
+                                 rows, r.TuP, sims, st));
+        HIPCHK(cbw_sim_resize_batch(sims, r.TuP, off_dev, (int)p0, pc, K, R, rows, L, Tu, Ho, Wo, (uint16_t*)cws, st));
+        CHK(resnet_chunk(h, plan, cws, pc, Ho, Wo, logits + (size_t)p0 * 2, st));
+    }
+    return CBW_OK;
+}
+
+int cbw_kws_sim_rows_bf16(const uint16_t* utt, int B, int Tu, const uint16_t* kwd, int R, int D, int L,
+                          const int32_t* off_dev, int K, int p0, int pc, int ld, float* rows, cbw_stream_t stream) {
+    if (!utt || !kwd || !off_dev || !rows) return fail(CBW_ERR_INVALID, "null argument");
+    if (D <= 0 || D % 64) return fail(CBW_ERR_INVALID, "D must be a multiple of 64");
+    if (Tu < 1 || R < 1 || L < 1 || L > 16 || K < 1 || B < 1 || (int64_t)B * K > INT32_MAX || p0 < 0 || pc < 1 ||
+        (int64_t)p0 + pc > (int64_t)B * K || ld < Tu)
+        return fail(CBW_ERR_INVALID, "bad sizes");
+    if ((uintptr_t)utt % 16 || (uintptr_t)kwd % 16) return fail(CBW_ERR_INVALID, "utt and kwd must be 16-byte aligned");
+    // without host offsets R bounds a run's rows and pc * R the chunk's
+    HIPCHK(cbw_sim_rows_bf16(utt, kwd, off_dev, B, K, R, L, Tu, D, p0, pc, R, (int64_t)pc * R, ld, rows,
+                             (hipStream_t)stream));
+    return CBW_OK;
+}
+
 int cbw_kws_profile(cbw_kws* h, int max_launches) {
     if (!h || max_launches < 0) return fail(CBW_ERR_INVALID, "bad arguments");
     for (auto e : h->prof.ev) (void)hipEventDestroy(e);
@@ -2101,18 +2198,21 @@ int64_t cbw_kws_rescore_resized_x3_workspace_bytes(cbw_kws* h, const int32_t* of
     return resized_exact_ws(h, off_host, K, Tu, D, Ho, Wo, true);
 }
 
-static int rescore_resized_impl(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D,
+// B = 1 with batch false: the per-utterance entry points, sel = keywords; batch: sel indexes the B * K pairs b * K + k
+static int rescore_resized_impl(cbw_kws* h, const float* utt, int B, bool batch, int Tu, const float* kwd, int R, int D,
                                 const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo,
                                 const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes, hipStream_t st,
                                 bool x3) {
     if (!h) return fail(CBW_ERR_INVALID, "null handle");
     if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_kws_finalize not called");
+    if (B < 1 || (int64_t)B * std::max(K, 0) > INT32_MAX) return fail(CBW_ERR_INVALID, "B must be >= 1 and B * K < 2^31");
     ResizedExact r;
     const int chunk = x3 ? resized_x3_chunk() : EXACT_CHUNK;
     CHK(resized_exact_args(h, off_host, K, Tu, R, D, Ho, Wo, chunk, r));
     if (h->stem32.cout == 0 || h->blocks3.empty())
         return fail(CBW_ERR_STATE, "no fp32 network: call cbw_kws_build_exact first");
     if (n_sel < 0) return fail(CBW_ERR_INVALID, "n_sel must be >= 0");
+    if (batch && n_sel > (int64_t)B * K) return fail(CBW_ERR_INVALID, "more pairs selected than B * K");
     if (n_sel == 0) return CBW_OK;
     if (K < 1) return fail(CBW_ERR_INVALID, "keywords selected but none given");
     if (!utt || !kwd || !off_dev || !sel || !logits || !ws) return fail(CBW_ERR_INVALID, "null argument");
@@ -2123,8 +2223,8 @@ static int rescore_resized_impl(cbw_kws* h, const float* utt, int Tu, const floa
     void* tier_ws = (char*)ws + r.rows_bytes;
     // a pass's maps: the similarity rows of its keywords (cb_whisper.py:196), resized to (Ho, Wo) (:206)
     auto fill = [&](int c0, int cn, float* maps) {
-        HIPCHK(cbw_sim_rows_f32(utt, kwd, off_dev, sel, c0, cn, K, R, L, Tu, D, r.tk_max, r.ld, rows, st));
-        HIPCHK(cbw_sim_resize_f32(rows, off_dev, sel, c0, cn, K, R, L, Tu, r.tk_max, r.ld, Ho, Wo, maps, st));
+        HIPCHK(cbw_sim_rows_f32(utt, B, kwd, off_dev, sel, c0, cn, K, R, L, Tu, D, r.tk_max, r.ld, rows, st));
+        HIPCHK(cbw_sim_resize_f32(rows, B, off_dev, sel, c0, cn, K, R, L, Tu, r.tk_max, r.ld, Ho, Wo, maps, st));
         return (int)CBW_OK;
     };
     if (x3) return rescore_x3_passes(h, Ho, Wo, chunk, sel, n_sel, logits, tier_ws, st, fill);
@@ -2134,15 +2234,32 @@ static int rescore_resized_impl(cbw_kws* h, const float* utt, int Tu, const floa
 int cbw_kws_rescore_resized(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D, const int32_t* off_dev,
                             const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel, int n_sel, float* logits,
                             void* ws, int64_t ws_bytes, cbw_stream_t stream) {
-    return rescore_resized_impl(h, utt, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws, ws_bytes,
-                                (hipStream_t)stream, false);
+    return rescore_resized_impl(h, utt, 1, false, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws,
+                                ws_bytes, (hipStream_t)stream, false);
 }
 
 int cbw_kws_rescore_resized_x3(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D,
                                const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel,
                                int n_sel, float* logits, void* ws, int64_t ws_bytes, cbw_stream_t stream) {
-    return rescore_resized_impl(h, utt, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws, ws_bytes,
-                                (hipStream_t)stream, true);
+    return rescore_resized_impl(h, utt, 1, false, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws,
+                                ws_bytes, (hipStream_t)stream, true);
+}
+
+// the two tiers for a batch of segments (cb_whisper.py:87-129): utt f32 [B][L][Tu][D], sel indexes the B * K pairs
+int cbw_kws_rescore_resized_batch(cbw_kws* h, const float* utt, int B, int Tu, const float* kwd, int R, int D,
+                                  const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo,
+                                  const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                                  cbw_stream_t stream) {
+    return rescore_resized_impl(h, utt, B, true, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws,
+                                ws_bytes, (hipStream_t)stream, false);
+}
+
+int cbw_kws_rescore_resized_x3_batch(cbw_kws* h, const float* utt, int B, int Tu, const float* kwd, int R, int D,
+                                     const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo,
+                                     const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                                     cbw_stream_t stream) {
+    return rescore_resized_impl(h, utt, B, true, Tu, kwd, R, D, off_dev, off_host, K, Ho, Wo, sel, n_sel, logits, ws,
+                                ws_bytes, (hipStream_t)stream, true);
 }
 
 // the two stages one by one (tests): rows f32 [n_sel][L][tk_max][ld], then maps f32 NHWC [n_sel][Ho][Wo][L]
@@ -2153,7 +2270,7 @@ int cbw_kws_sim_rows_f32(const float* utt, int Tu, const float* kwd, int R, int 
     if (Tu < 1 || R < 1 || L < 1 || L > 16 || K < 1 || n_sel < 1 || n_sel > 65535 || tk_max < 1 || ld < Tu)
         return fail(CBW_ERR_INVALID, "bad sizes");
     if ((uintptr_t)utt % 16 || (uintptr_t)kwd % 16) return fail(CBW_ERR_INVALID, "utt and kwd must be 16-byte aligned");
-    HIPCHK(cbw_sim_rows_f32(utt, kwd, off_dev, sel, 0, n_sel, K, R, L, Tu, D, tk_max, ld, rows, (hipStream_t)stream));
+    HIPCHK(cbw_sim_rows_f32(utt, 1, kwd, off_dev, sel, 0, n_sel, K, R, L, Tu, D, tk_max, ld, rows, (hipStream_t)stream));
     return CBW_OK;
 }
 
@@ -2162,7 +2279,8 @@ int cbw_kws_sim_resize_f32(const float* rows, int Tu, int R, int L, const int32_
     if (!rows || !off_dev || !sel || !maps) return fail(CBW_ERR_INVALID, "null argument");
     if (Tu < 1 || R < 1 || L < 1 || L > 16 || K < 1 || n_sel < 1 || tk_max < 1 || ld < Tu || Ho < 1 || Wo < 1)
         return fail(CBW_ERR_INVALID, "bad sizes");
-    HIPCHK(cbw_sim_resize_f32(rows, off_dev, sel, 0, n_sel, K, R, L, Tu, tk_max, ld, Ho, Wo, maps, (hipStream_t)stream));
+    HIPCHK(cbw_sim_resize_f32(rows, 1, off_dev, sel, 0, n_sel, K, R, L, Tu, tk_max, ld, Ho, Wo, maps,
+                              (hipStream_t)stream));
     return CBW_OK;
 }
 

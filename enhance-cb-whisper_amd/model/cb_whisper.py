@@ -299,6 +299,19 @@ class CBWhisper:
         pk[:, :, : input_features.shape[1]] = input_features.to(dev).transpose(1, 2).to(torch.bfloat16)
         hs = enc.hidden_states(pk, self.layer_ids, normalize=True)     # [S, L, 1500, D]
         out = []
+        if self.cnn is not None and self.kws_features_size is not None and S > 1:
+            # every segment against every keyword in one pass (KWSModel.spot_keywords_batch); the "auto" band is
+            # calibrated on the first segment before it, as the loop below does at s = 0, so the decisions are the
+            # loop's
+            if self._packed is None:
+                self._packed = pack_keywords(self.keyword_hs, dev)
+            if self.exact_band > 0 and self._packed32 is None:
+                self._packed32 = pack_keywords(self.keyword_hs, dev, dtype=torch.float32)
+            self._calibrate_cnn_band(hs[0], self._packed, self._packed32, self.kws_features_size)
+            for idx in self.cnn.spot_keywords_batch(hs, self._packed, self.kws_features_size,
+                                                    exact_band=self.exact_band, kwd_hs32=self._packed32):
+                out.append([self.keywords[i] for i in sorted(set(idx))])
+            return out
         for s in range(S):
             if self.cnn is not None:
                 # exact_band > 0: the keywords near p = 0.5 re-scored in fp32 from the fp32 hidden states, as the

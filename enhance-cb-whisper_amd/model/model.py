@@ -137,3 +137,39 @@ class KWSModel:
         logits = self.score_keywords(utt_hs, kwd_hs, kws_features_size, exact_band, kwd_hs32, band_x3)
         _, idx = spot(logits, None, 0.5, mode="argmax")
         return idx.tolist()
+
+    def score_keywords_batch(self, utt_hs: torch.Tensor, kwd_hs, kws_features_size=(150, 750), exact_band: float = 0.0,
+                             kwd_hs32=None, band_x3: Optional[float] = 1e-4) -> torch.Tensor:
+        """``score_keywords`` for the batch of segments keyword_spotting receives (cb_whisper.py:87-129): utt_hs
+        [S, 12, Tu, D] -> logits [S, K, 2] in one pass (KwsEngine.score_resized_batch / score_resized_batch_exact);
+        row s carries the bits ``score_keywords(utt_hs[s], ...)`` gives.  ``exact_band``, ``kwd_hs32`` and
+        ``band_x3`` as there; ``last_exact_stats`` holds the sums over the segments."""
+        kh = kwd_hs if isinstance(kwd_hs, tuple) else list(kwd_hs)
+        eng = self.engine(int(utt_hs.shape[-1]))
+        size = tuple(kws_features_size)
+        self.last_exact_stats = None
+        if not exact_band or exact_band <= 0:
+            return eng.score_resized_batch(utt_hs, kh, size)
+        if kwd_hs32 is None:
+            if isinstance(kh, tuple):
+                raise ValueError("exact_band > 0 with packed bf16 keywords needs kwd_hs32, their fp32 packing")
+            kwd_hs32 = pack_keywords(kh, eng.device, dtype=torch.float32)
+        if not eng.has_exact_resized:
+            eng.build_exact()
+        logits, self.last_exact_stats = eng.score_resized_batch_exact(utt_hs, kh, kwd_hs32, size, float(exact_band),
+                                                                      band_x3=band_x3)
+        return logits
+
+    def spot_keywords_batch(self, utt_hs: torch.Tensor, kwd_hs, kws_features_size=(150, 750),
+                            exact_band: float = 0.0, kwd_hs32=None,
+                            band_x3: Optional[float] = 1e-4) -> List[List[int]]:
+        """cb_whisper.py:128 per segment: one list of indices with argmax(logits) == 1 for each of the S segments."""
+        logits = self.score_keywords_batch(utt_hs, kwd_hs, kws_features_size, exact_band, kwd_hs32, band_x3)
+        S, K = logits.shape[0], logits.shape[1]
+        if S * K == 0:
+            return [[] for _ in range(S)]
+        _, idx = spot(logits.view(S * K, 2), None, 0.5, mode="argmax")   # sorted pair indices s * K + k
+        out: List[List[int]] = [[] for _ in range(S)]
+        for p in idx.tolist():
+            out[p // K].append(p % K)
+        return out

@@ -125,6 +125,27 @@ int cbw_kws_score_resized(cbw_kws* h, const uint16_t* utt, int Tu, const uint16_
                           const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, float* logits,
                           int chunk, void* ws, int64_t ws_bytes, cbw_stream_t stream);
 
+/* The same spotter for a batch of segments in one pass (model/cb_whisper.py:87-129, :189-210: keyword_spotting
+ * receives [S, n_mel, 3000] and scores every segment against every keyword).  utt bf16 [B][L][Tu][D]; kwd, off_dev
+ * and off_host as cbw_kws_score_resized; logits f32 [B][K][2], pair p = b * K + k (the layout of
+ * cbw_kws_score_pairs without index arrays).  chunk counts pairs: a chunk may start and end inside an utterance and
+ * span several.  Per chunk one launch computes the similarity rows of all n_layers layers straight from utt (no
+ * padded copy of the utterances), one the resize, then the ResNet.  Row b of logits is bit-identical to what
+ * cbw_kws_score_resized writes for utterance b alone, whatever chunk is and whatever else the batch holds.
+ * Checked in cbw_kws_score_resized's order, B < 1 with the sizes (CBW_ERR_INVALID); K == 0 returns CBW_OK and
+ * writes nothing; a short workspace is CBW_ERR_OOM.  No allocation, no synchronisation, one stream.              */
+int64_t cbw_kws_score_resized_batch_workspace_bytes(cbw_kws* h, const int32_t* off_host, int K, int B, int Tu, int D,
+                                                    int Ho, int Wo, int chunk);
+int cbw_kws_score_resized_batch(cbw_kws* h, const uint16_t* utt, int B, int Tu, const uint16_t* kwd, int R, int D,
+                                const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, float* logits,
+                                int chunk, void* ws, int64_t ws_bytes, cbw_stream_t stream);
+/* its first stage alone (tests): the similarity rows (cb_whisper.py:196) of pairs [p0, p0 + pc) of the B * K into
+ * rows f32 [L][chunk rows][ld], the chunk's keywords' frames one after another in pair order; row t < Tk_k and
+ * column u < Tu of each pair written, nothing else.  bf16 MFMA, fp32 accumulation, k ascending.  Refused before
+ * any launch (CBW_ERR_INVALID): a null pointer, D % 64, ld < Tu, L > 16, B < 1, pc < 1, p0 + pc > B * K.        */
+int cbw_kws_sim_rows_bf16(const uint16_t* utt, int B, int Tu, const uint16_t* kwd, int R, int D, int L,
+                          const int32_t* off_dev, int K, int p0, int pc, int ld, float* rows, cbw_stream_t stream);
+
 /* fp32 re-scoring (exact decisions; the reference evaluates in fp32, eval-*-comp-*.yaml precision
  * 32-true).  Same forward as cbw_kws_project / cbw_kws_score, every tensor fp32 and every conv on the
  * fp32-input MFMA (exact products, fp32 accumulation), BN folded in fp32, no conv fusion:
@@ -206,6 +227,23 @@ int64_t cbw_kws_rescore_resized_x3_workspace_bytes(cbw_kws* h, const int32_t* of
 int cbw_kws_rescore_resized_x3(cbw_kws* h, const float* utt, int Tu, const float* kwd, int R, int D,
                                const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo, const int32_t* sel,
                                int n_sel, float* logits, void* ws, int64_t ws_bytes, cbw_stream_t stream);
+/* the two tiers for a batch of segments (cb_whisper.py:87-129): utt f32 [B][L][Tu][D]; sel (device int32 [n_sel])
+ * indexes the P = B * K pairs p = b * K + k, the rows of logits f32 [B * K][2] (cbw_kws_score_resized_batch's
+ * layout).  logits[sel[i]] <- the tier's logits of pair sel[i]: bit-identical to the per-utterance call's for that
+ * utterance and keyword; rows not selected are not written.  sel is clamped into [0, B * K) on the device before an
+ * operand is read; the row written is sel[i] itself.  Checks as above, and CBW_ERR_INVALID for B < 1 and
+ * n_sel > B * K; n_sel == 0 returns CBW_OK.  Workspace: cbw_kws_rescore_resized_workspace_bytes /
+ * cbw_kws_rescore_resized_x3_workspace_bytes (a pass's size does not depend on B).  The host-blocking dispatch
+ * throttle of cbw_kws_rescore applies unchanged: outside graph capture, a call over more than 256 selected pairs
+ * waits on the host so that at most 16 passes are in flight.  The per-utterance calls are the B = 1 case.        */
+int cbw_kws_rescore_resized_batch(cbw_kws* h, const float* utt, int B, int Tu, const float* kwd, int R, int D,
+                                  const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo,
+                                  const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                                  cbw_stream_t stream);
+int cbw_kws_rescore_resized_x3_batch(cbw_kws* h, const float* utt, int B, int Tu, const float* kwd, int R, int D,
+                                     const int32_t* off_dev, const int32_t* off_host, int K, int Ho, int Wo,
+                                     const int32_t* sel, int n_sel, float* logits, void* ws, int64_t ws_bytes,
+                                     cbw_stream_t stream);
 /* the two stages of a pass one by one (tests): rows f32 [n_sel][L][tk_max][ld] (ld >= Tu; row t < Tk_k and column
  * u < Tu of map i = keyword sel[i] written, cb_whisper.py:196), then maps f32 NHWC [n_sel][Ho][Wo][L]
  * (cb_whisper.py:206).  tk_max bounds the keyword lengths read; D % 16 == 0, L <= 16.                           */

@@ -4,7 +4,11 @@ RS_MODE=cnn12: the exact tiers of CB-Whisper's own 12-channel spotter instead (c
 ragged keywords (20-192 frames) of D 1280 against 1500 utterance frames, maps (150, 750); per tier the time per
 selected keyword, the share of it the fp32 front takes (similarity rows + resize, timed alone over the same passes of
 32), and the bf16 pass (cbw_kws_score_resized) over the same keywords beside them.  HIP events around RS_REPS calls
-after a warm-up call."""
+after a warm-up call.
+
+RS_MODE=cnn12_batch: RS_B (4) segments against RS_K (1000) such keywords in one pass (cbw_kws_score_resized_batch,
+KwsEngine.score_resized_batch_exact at a band of 3 % of the pairs) against the loop of per-utterance calls, each of
+RS_REPS calls timed on its own, and sim_rows_bf16_kernel alone on RS_PC (64) pairs."""
 import os
 import sys
 import time
@@ -82,8 +86,84 @@ def cnn12():
               f"{t / t16:.1f} x the bf16 pass")
 
 
+def each(fn, reps):
+    """Milliseconds of each of reps calls of fn() (one event pair per call), after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def cnn12_batch():
+    """RS_MODE=cnn12_batch: B segments against RS_K ragged keywords in one pass (cbw_kws_score_resized_batch,
+    KwsEngine.score_resized_batch_exact) against the loop of B per-utterance calls, both in this process; then
+    sim_rows_bf16_kernel alone on one chunk of pairs."""
+    reps = int(os.environ.get("RS_REPS", "3"))
+    K, B = int(os.environ.get("RS_K", "1000")), int(os.environ.get("RS_B", "4"))
+    L, D, Tu, size = 12, 1280, 1500, (150, 750)
+    hp = dict(n_layers=L, embedding_dim=D, learn_features=False, proj_mlp=False)
+    eng = KwsEngine(hp, synth.synth_kws_state_dict(seed=3, **hp)).build_exact()
+    d = eng.device
+    g = torch.Generator(device=d).manual_seed(0)
+    lens = torch.randint(20, 193, (K,), generator=torch.Generator().manual_seed(0)).tolist()
+    utt = torch.randn((B, L, Tu, D), generator=g, device=d)
+    utt = utt / utt.norm(dim=-1, keepdim=True)
+    kwd = []
+    for T in lens:
+        k = torch.randn((L, T, D), generator=g, device=d)
+        kwd.append(k / k.norm(dim=-1, keepdim=True))
+    p32 = pack_keywords(kwd, d, dtype=torch.float32)
+    p16 = pack_keywords(kwd, d)
+    del kwd
+    utt16 = utt.to(torch.bfloat16)
+
+    def fmt(ts):
+        return f"{sum(ts) / len(ts):.1f} ms (" + ", ".join(f"{t:.1f}" for t in ts) + ")"
+    print(f"cnn12_batch B {B}, K {K} keywords, mean {sum(lens) / K:.0f} frames, chunk "
+          f"{eng.default_chunk(*size, budget_bytes=1 << 30)}")
+    loop = each(lambda: [eng.score_resized(utt16[b], p16, size) for b in range(B)], reps)
+    batch = each(lambda: eng.score_resized_batch(utt16, p16, size), reps)
+    print(f"  bf16 pass: loop of {B} score_resized {fmt(loop)}; score_resized_batch {fmt(batch)}; batch / loop "
+          f"{sum(batch) / sum(loop):.3f}, loop spread {(max(loop) - min(loop)) / (sum(loop) / reps) * 100:.1f} %")
+    # a band that selects a few percent of the pairs
+    lg = eng.score_resized_batch(utt16, p16, size)
+    dist = (torch.softmax(lg.view(-1, 2).double(), -1)[:, 1] - 0.5).abs()
+    band = float(torch.quantile(dist, 0.03))
+    n_in = int((dist <= band).sum())
+    loop = each(lambda: [eng.score_resized_exact(utt[b], p16, p32, size, band) for b in range(B)], reps)
+    batch = each(lambda: eng.score_resized_batch_exact(utt, p16, p32, size, band), reps)
+    print(f"  cascade, band {band:.3e} ({n_in} of {B * K} pairs): loop of {B} score_resized_exact {fmt(loop)}; "
+          f"score_resized_batch_exact {fmt(batch)}; batch / loop {sum(batch) / sum(loop):.3f}, loop spread "
+          f"{(max(loop) - min(loop)) / (sum(loop) / reps) * 100:.1f} %")
+    # the rows kernel alone: one chunk of pairs that straddles an utterance boundary
+    rows_k, off = p16
+    off_dev = off.to(d)
+    pc = min(int(os.environ.get("RS_PC", "64")), B * K)
+    p0 = max(0, min(K - pc // 2, B * K - pc))
+    n_rows = sum(lens[p % K] for p in range(p0, p0 + pc))
+    ld = (Tu + 127) // 128 * 128
+    rows = torch.empty((L, n_rows, ld), device=d)
+    st = _lib.stream_handle()
+    t = timed(lambda: _lib.check(eng.lib.cbw_kws_sim_rows_bf16(utt16.data_ptr(), B, Tu, rows_k.data_ptr(),
+                                                               rows_k.shape[1], D, L, off_dev.data_ptr(), K, p0, pc, ld,
+                                                               rows.data_ptr(), st), "cbw_kws_sim_rows_bf16"), 10)
+    fl = 2.0 * L * n_rows * Tu * D
+    print(f"  sim_rows_bf16_kernel alone, pairs [{p0}, {p0 + pc}) = {n_rows} rows: {t * 1e3:.0f} us, "
+          f"{fl / t / 1e9:.1f} TFLOP/s ({fl / pc / 1e9:.1f} GFLOP per pair)")
+
+
 if os.environ.get("RS_MODE") == "cnn12":
     cnn12()
+    sys.exit(0)
+if os.environ.get("RS_MODE") == "cnn12_batch":
+    cnn12_batch()
     sys.exit(0)
 
 hp = dict(n_layers=3, embedding_dim=1280, learn_features=True, proj_mlp=True, frames_conv=True)
