@@ -116,6 +116,11 @@ SIGNATURES = {
     "cbw_conv1x1_dual": (c_int, [c_void_p] * 6 + [c_int] * 10 + [c_void_p]),
     "cbw_gemm_splitk_factor": (c_int, [c_int, c_int, c_int]),
     "cbw_gemm": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_int64, c_void_p]),
+    "cbw_linear_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                                                c_void_p]),
+    "cbw_linear_rows_kernel": (c_char_p, [c_int, c_int, c_int, c_int]),
+    "cbw_layernorm_rows": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p]),
     "cbw_encoder_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "cbw_kws_profile": (c_int, [c_void_p, c_int]),
     "cbw_decoder_create": (c_int, [ctypes.POINTER(DecoderConfig), ctypes.POINTER(c_void_p)]),

@@ -16,13 +16,14 @@
 //     partials, no atomics.
 #include "cbw_common.h"
 #include "cbw_kernels.h"
+#include "gemv_route.h"
 
 namespace {
 
-constexpr int GV_BATCH = 10;   // k-steps (of 32) in flight per wave
-
-constexpr int GV_LN_MAXK = 1280;   // LayerNorm prologue: a row is <= 5 f32x4 per lane (Whisper d_model <= 1280)
-constexpr int GV_LN_LDS = 48 * 1024;   // + the 16 KB reduction buffer: within the 64 KB default
+// GV_BATCH, GV_LN_MAXK, GV_LN_LDS, GD_MAXM, GD_LDS16: gemv_route.h (the dispatch sizes its launches by them)
+static_assert(sizeof(f32x4) * 16 * 64 + GV_LN_LDS <= GV_LDS_DEFAULT, "gemv_kernel<true>: red[16][64] + the padded rows");
+static_assert(GV_LN_MAXK % 256 == 0 && gemv_waves(GV_LN_MAXK) * 64 <= 512, "gemv_kernel<true>: launch bounds");
+static_assert(gemv_waves(16 * GV_BATCH * 32) == 16 && gemv_waves(GV_BATCH * 32) == 1, "a wave owns <= GV_BATCH k-steps");
 
 // LN: the LayerNorm-prologue instance (K <= 1280 -> at most 8 waves, so a wider register budget)
 template <bool LN>
@@ -158,15 +159,19 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void gemv_kernel(GemvArgs a) {
 // exchanges in a fixed order (deterministic).  Versus the MFMA kernel above (16 columns per workgroup, 16 - M of its
 // 16 B-operand rows padding): 2x the workgroups at the decode step's N (160 at D 1280 instead of 80), so twice the
 // CUs stream the weights; the step is latency-bound on the chain of its ~300 launches.
-constexpr int GD_MAXM = 8;   // K <= 5120
-// 9..16 rows: the 16-row instantiation, its rows staged in up to 158 KB of LDS (gfx950: 160 KB per workgroup)
-constexpr int GD_LDS16 = 158 * 1024;
+// GD_MAXM = 8 rows (K <= 5120); 9..16 rows: the 16-row instantiation, its rows staged in up to GD_LDS16 = 158 KB of LDS
+// (gfx950: 160 KB per workgroup)
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+
+constexpr bool wait_vm_has(int n) {
+    for (int c : GD_WAIT_COUNTS)
+        if (c == n) return true;
+    return false;
+}
 
 template <int N>
 CBW_DEV void wait_vm() {   // s_waitcnt vmcnt(N) for the counts the kernel below uses
-    static_assert(N == 3 || N == 4 || N == 5 || N == 6 || N == 8 || N == 10 || N == 12 || N == 16 || N == 20 || N == 24 ||
-                      N == 32 || N == 40, "count");
+    static_assert(wait_vm_has(N), "count");   // GD_WAIT_COUNTS (gemv_route.h): the route check walks the same list
     if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
@@ -342,95 +347,57 @@ __global__ __launch_bounds__(WV * 64) void gemv_dot_kernel(GemvArgs a) {   // NJ
 
 }  // namespace
 
-int cbw_gemv_waves(int K) {   // enough waves that each owns <= GV_BATCH k-steps (one burst of loads), at most 16
-    const int ks = K / 32;
-    int W = 1;
-    while (W < 16 && (ks + W - 1) / W > GV_BATCH) W *= 2;
-    return W;
-}
+int cbw_gemv_waves(int K) { return gemv_waves(K); }
+bool cbw_gemv_ln_ok(int M, int K) { return gemv_ln_ok(M, K); }
 
 namespace {
-// the 16-row instantiations stage up to GD_LDS16 of rows: above the 64 KB default, raised once per kernel
-template <auto KERNEL, int MAXM>
-void dot_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemvArgs& a) {
-    if constexpr (MAXM > GD_MAXM) {
-        static const bool once =
-            hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, GD_LDS16) == hipSuccess;
+// One instantiation of the dot kernel, launched as the route says.  The route's template arguments for this
+// instantiation's (rows, K, LN) must be this instantiation's: checked here at compile time, so the header cannot
+// drift from the kernels.  raise_lds: above the 64 KB default the limit is raised once per kernel.
+template <bool LN, int NJ, int CPW, int MAXM, int KS, int WV>
+hipError_t dot_launch(const GemvRoute& r, const GemvArgs& a, hipStream_t st) {
+    constexpr GemvRoute R = gemv_route(MAXM, 4, NJ * 256, LN);
+    static_assert(R.kernel == GemvKernel::Dot && R.ln == LN && R.nj == NJ && R.cpw == CPW && R.maxm == MAXM &&
+                      R.ks == KS && R.wv == WV && R.block == WV * 64 && R.cols == WV * CPW, "gemv_route.h");
+    static_assert(LN || wait_vm_has(NJ * 256 / (512 / CPW)), "NL is one of wait_vm's counts");
+    if (r.raise_lds) {
+        static const bool once = hipFuncSetAttribute((const void*)gemv_dot_kernel<LN, NJ, CPW, MAXM, KS, WV>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, GD_LDS16) == hipSuccess;
         (void)once;
     }
-    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, a);
-}
-
-// rows 0..7 run the same arithmetic in either instantiation (each row's sums are independent of M and of the wave
-// count), so a step over several windows' beams gives each window's rows the values a step over that window alone
-// gives.  One column per wave for the K 5120 Linear (fc2, no LayerNorm); its 9..16-row rows staged in two K halves.
-template <int NJ, int MAXM, int WV>
-hipError_t launch_dot_m(const GemvArgs& a, size_t lds, hipStream_t st) {
-    const dim3 block(WV * 64);
-    const dim3 grid2((a.N + WV * 2 - 1) / (WV * 2)), grid1((a.N + WV - 1) / WV);
-    if constexpr (NJ * 256 <= GV_LN_MAXK) {
-        if (a.xf) {
-            dot_launch<gemv_dot_kernel<true, NJ, 2, MAXM, 1, WV>, MAXM>(grid2, block, lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    if (a.xf) return hipErrorInvalidValue;   // gemv_dot_wanted admits a LayerNorm prologue only for K <= 1280
-    if constexpr (NJ == 20) {
-        if constexpr (MAXM > GD_MAXM) {   // rows staged in two K halves
-            const size_t lds2 = ((size_t)a.M * (a.K / 2) * 2 + 1023) / 1024 * 1024;
-            dot_launch<gemv_dot_kernel<false, NJ, 1, MAXM, 2, WV>, MAXM>(grid1, block, lds2, st, a);
-        } else {
-            dot_launch<gemv_dot_kernel<false, NJ, 1, MAXM, 1, WV>, MAXM>(grid1, block, lds, st, a);
-        }
-        return hipGetLastError();
-    }
-    dot_launch<gemv_dot_kernel<false, NJ, 2, MAXM, 1, WV>, MAXM>(grid2, block, lds, st, a);
+    hipLaunchKernelGGL((gemv_dot_kernel<LN, NJ, CPW, MAXM, KS, WV>), dim3(r.grid), dim3(r.block), r.lds, st, a);
     return hipGetLastError();
-}
-
-template <int NJ>
-hipError_t launch_dot(const GemvArgs& a, size_t lds, hipStream_t st) {
-    if (a.M <= GD_MAXM) return launch_dot_m<NJ, GD_MAXM, 4>(a, lds, st);
-    return launch_dot_m<NJ, 16, 8>(a, lds, st);   // eight computing waves for 9..16 rows
-}
-
-bool gemv_dot_wanted(const GemvArgs& a) {
-    const int nj = a.K / 256;
-    const bool nj_ok = nj == 3 || nj == 4 || nj == 5 || nj == 12 || nj == 16 || nj == 20;
-    const size_t lds_max = a.M <= GD_MAXM ? 64 * 1024 : GD_LDS16;
-    return a.M <= 16 && a.K % 256 == 0 && nj_ok && (size_t)a.M * (a.K + 8) * 2 <= lds_max &&
-           (!a.xf || a.K <= GV_LN_MAXK) && a.ldx % 8 == 0;
 }
 }  // namespace
 
-bool cbw_gemv_ln_ok(int M, int K) {
-    return M >= 1 && M <= 16 && K % 32 == 0 && K <= GV_LN_MAXK && (size_t)M * (K + 8) * 2 <= GV_LN_LDS;
-}
-
+// Launches what gemv_route (gemv_route.h) says and nothing else.  The kernel family -- MFMA or dot -- depends on (K,
+// LayerNorm prologue) alone, never on the row count, and within the dot family rows 0..7 run the same arithmetic in
+// the 8-row and the 16-row instantiation (each row's sums are independent of M, of the wave count and of the K
+// stages), so a step over several windows' beams gives each window's rows the values a step over that window alone
+// gives, bit for bit (tests/test_gpu_gemv.py: every row count 1..16 at every width).  One column per wave for the K
+// 5120 Linear (fc2, no LayerNorm); its 9..16-row rows staged in two K halves, its 7 and 8 rows (70 / 80 KB) under the
+// raised LDS limit on the instantiation rows 1..6 run.
 hipError_t cbw_gemv(const GemvArgs& a, hipStream_t st) {
     if (a.M < 1 || a.M > 16 || a.K % 32 || a.N % 4 || a.ldx % 8 || a.ldy % 4 || (a.res && a.res_ld % 4))
         return hipErrorInvalidValue;
     if (a.xf && (!a.ln_g || !a.ln_b || a.ldx % 4 || !cbw_gemv_ln_ok(a.M, a.K))) return hipErrorInvalidValue;
     if (a.kv_k && (!a.kv_v || a.kv_D % 4 || a.N != 3 * a.kv_D || a.kv_ld % 4 || (a.flags & CBW_EPI_OUT_F32)))
         return hipErrorInvalidValue;
-    if (gemv_dot_wanted(a)) {
-        // LayerNorm prologue: padded rows [M][K + 8]; else rows packed [M][K], DMA'd in whole 1 KB pieces
-        const size_t lds = a.xf ? (size_t)a.M * (a.K + 8) * 2 : ((size_t)a.M * a.K * 2 + 1023) / 1024 * 1024;
-        switch (a.K / 256) {
-#define GD_CASE(NJ) \
-    case NJ: return launch_dot<NJ>(a, lds, st);
-            GD_CASE(3) GD_CASE(4) GD_CASE(5) GD_CASE(12) GD_CASE(16) GD_CASE(20)
-#undef GD_CASE
-            default: break;
-        }
+    const GemvRoute r = gemv_route(a.M, a.N, a.K, a.xf != nullptr);
+    if (r.kernel == GemvKernel::Mfma) {
+        if (r.ln) hipLaunchKernelGGL(gemv_kernel<true>, dim3(r.grid), dim3(r.block), r.lds, st, a);
+        else hipLaunchKernelGGL(gemv_kernel<false>, dim3(r.grid), dim3(r.block), r.lds, st, a);
+        return hipGetLastError();
     }
-    const int W = cbw_gemv_waves(a.K);
-    const size_t lds = a.xf ? (size_t)a.M * (a.K + 8) * 2 : 0;
-    if (a.xf) {
-        if (W > 8) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(gemv_kernel<true>, dim3((a.N + 15) / 16), dim3(64 * W), lds, st, a);
-    } else {
-        hipLaunchKernelGGL(gemv_kernel<false>, dim3((a.N + 15) / 16), dim3(64 * W), 0, st, a);
-    }
-    return hipGetLastError();
+    if (r.kernel != GemvKernel::Dot) return hipErrorInvalidValue;
+#define GD_TRY(LN, NJ, CPW, MAXM, KS, WV)                                                         \
+    if (r.ln == LN && r.nj == NJ && r.cpw == CPW && r.maxm == MAXM && r.ks == KS && r.wv == WV) \
+        return dot_launch<LN, NJ, CPW, MAXM, KS, WV>(r, a, st);
+#define GD_TRY_M(LN, NJ) GD_TRY(LN, NJ, 2, GD_MAXM, 1, 4) GD_TRY(LN, NJ, 2, 16, 1, 8)
+    GD_TRY_M(true, 3) GD_TRY_M(true, 4) GD_TRY_M(true, 5)
+    GD_TRY_M(false, 3) GD_TRY_M(false, 4) GD_TRY_M(false, 5) GD_TRY_M(false, 12) GD_TRY_M(false, 16)
+    GD_TRY(false, 20, 1, GD_MAXM, 1, 4) GD_TRY(false, 20, 1, 16, 2, 8)
+#undef GD_TRY_M
+#undef GD_TRY
+    return hipErrorInvalidValue;   // a route no instantiation matches: a missing kernel is an error
 }

@@ -17,6 +17,7 @@
 #include "cbw.h"
 #include "cbw_kernels.h"
 #include "conv_route.h"
+#include "gemv_route.h"
 
 namespace {
 
@@ -3226,6 +3227,45 @@ int cbw_gemm(const uint16_t* x, const uint16_t* w, const float* bias, const void
         if (N % 128 || S > K / 64) return fail(CBW_ERR_INVALID, "cbw_gemm: split-K needs N % 128 == 0 and S <= K / 64");
     }
     HIPCHK(cbw_conv_igemm_splitk(a, S, partial, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int cbw_linear_rows(const uint16_t* x, const float* xf, int ldx, const float* ln_g, const float* ln_b, float ln_eps,
+                    const uint16_t* w, const float* bias, const void* res, int res_ld, void* y, int ldy, int M, int N,
+                    int K, int flags, uint16_t* kv_k, uint16_t* kv_v, int64_t kv_ld, int kv_D, const int32_t* kv_pos,
+                    int kv_pos_rows, cbw_stream_t stream) {
+    if ((!x && !xf) || !w || !y) return fail(CBW_ERR_INVALID, "cbw_linear_rows: null operand");
+    if (M < 1 || M > 16 || N < 4 || N % 4 || K < 32 || K % 32 || ldx % 8 || ldy % 4 || ldx < K || ldy < N ||
+        (res && (res_ld % 4 || res_ld < N)))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows: 1 <= M <= 16, K % 32, N % 4, ldx % 8, ldy % 4, res_ld % 4");
+    if (flags & ~(CBW_EPI_RELU | CBW_EPI_GELU | CBW_EPI_RES_F32 | CBW_EPI_OUT_F32 | CBW_EPI_RES_AFTER_ACT))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows: unknown flag");
+    if (xf && (!ln_g || !ln_b || !cbw_gemv_ln_ok(M, K)))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows: the LayerNorm prologue needs gamma, beta and K <= 1280");
+    if (kv_k && (!kv_v || kv_D <= 0 || kv_D % 4 || N != 3 * kv_D || kv_ld % 4 || kv_ld < kv_D || (flags & CBW_EPI_OUT_F32)))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows: K/V append needs kv_v, N == 3 kv_D, kv_D % 4, kv_ld % 4, bf16 output");
+    if (gemv_route(M, N, K, xf != nullptr).kernel == GemvKernel::Invalid)
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows: no kernel for this shape");
+    GemvArgs a{};
+    a.x = xf ? nullptr : (const bf16*)x; a.ldx = ldx; a.w = (const bf16*)w; a.bias = bias;
+    a.res = res; a.res_ld = res_ld; a.y = y; a.ldy = ldy;
+    a.M = M; a.N = N; a.K = K; a.flags = flags;
+    a.xf = xf; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
+    if (kv_k) {
+        a.kv_k = (bf16*)kv_k; a.kv_v = (bf16*)kv_v; a.kv_ld = kv_ld; a.kv_D = kv_D;
+        a.kv_pos = kv_pos; a.kv_pos_rows = kv_pos_rows;
+    }
+    HIPCHK(cbw_gemv(a, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+const char* cbw_linear_rows_kernel(int M, int N, int K, int ln) { return gemv_route(M, N, K, ln != 0).name; }
+
+int cbw_layernorm_rows(const float* x, const float* g, const float* b, uint16_t* y, float* y32, int rows, int D,
+                       float eps, cbw_stream_t stream) {
+    if (!x || !g || !b || (!y && !y32) || rows <= 0 || D <= 0 || D % 4)
+        return fail(CBW_ERR_INVALID, "cbw_layernorm_rows: null operand, empty shape or D % 4 != 0");
+    HIPCHK(cbw_layernorm(x, g, b, y, y32, rows, D, eps, (hipStream_t)stream));
     return CBW_OK;
 }
 

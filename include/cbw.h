@@ -471,6 +471,30 @@ int cbw_conv1x1_dual(const uint16_t* x, const uint16_t* x2, const uint16_t* w, c
 int cbw_gemm_splitk_factor(int M, int K, int N);
 int cbw_gemm(const uint16_t* x, const uint16_t* w, const float* bias, const void* res, void* y, int M, int K, int N,
              int flags, int ksplit, float* partial, int64_t partial_floats, cbw_stream_t stream);
+/* One Linear of a decode step as cbw_decoder_step* launches it (building block for the tests): the skinny GEMM over
+ * 1 <= M <= 16 rows, y[m][n] = act(sum_k x[m][k] w[n][k] + bias[n] (+ res[m][n])), fp32 accumulation; asynchronous.
+ *   rows: x bf16 [M] rows of pitch ldx, or (x NULL) xf f32 [M] rows of pitch ldx normalised over K in the kernel's
+ *     prologue with ln_g / ln_b f32 [K] and ln_eps, exactly as cbw_layernorm_rows computes them (K <= 1280);
+ *   w bf16 [N][K]; bias f32 [N] or NULL; res (or NULL) bf16, or f32 with flag 4, rows of pitch res_ld; y bf16, or f32
+ *     with flag 8, rows of pitch ldy; flags as cbw_conv2d (1 ReLU, 2 GELU, 4, 8, 16 = residual after the activation);
+ *   K/V append (kv_k NULL: none): N = 3 kv_D, bf16 output; columns [kv_D, 2 kv_D) of row m also go to
+ *     kv_k + m * kv_ld + pos * kv_D and [2 kv_D, 3 kv_D) to kv_v likewise, pos = 0 (kv_pos NULL), kv_pos[0] (device
+ *     int32, kv_pos_rows 0) or kv_pos[m] (kv_pos_rows 1).
+ * K % 32 == 0, N % 4 == 0, ldx % 8 == 0, ldy, res_ld, kv_D, kv_ld % 4 == 0; x / xf, w, y 16-byte aligned.
+ * Which kernel runs depends on (K, prologue or not) alone -- K 768, 1024, 1280, 3072, 4096, 5120 the VALU dot kernel,
+ * every other K the MFMA kernel -- and never on M: row m of an M-row call carries the bits of a 1-row call on row m
+ * alone (the guarantee cbw_decoder_step_rows gives).  cbw_linear_rows_kernel returns the name of the kernel a shape
+ * runs, template arguments included (ln 0/1: with the prologue), "" for a shape cbw_linear_rows rejects. */
+int cbw_linear_rows(const uint16_t* x, const float* xf, int ldx, const float* ln_g, const float* ln_b, float ln_eps,
+                    const uint16_t* w, const float* bias, const void* res, int res_ld, void* y, int ldy, int M, int N,
+                    int K, int flags, uint16_t* kv_k, uint16_t* kv_v, int64_t kv_ld, int kv_D, const int32_t* kv_pos,
+                    int kv_pos_rows, cbw_stream_t stream);
+const char* cbw_linear_rows_kernel(int M, int N, int K, int ln);
+/* The decoder's (and encoder's) LayerNorm launch (building block for the tests): x f32 [rows][D] -> y bf16 [rows][D]
+ * and / or y32 f32 [rows][D] (either may be NULL, not both) = (x - mean) * rsqrt(var + eps) * g + b, one wave per row,
+ * fp32; D % 4 == 0, operands 16-byte aligned; asynchronous. */
+int cbw_layernorm_rows(const float* x, const float* g, const float* b, uint16_t* y, float* y32, int rows, int D,
+                       float eps, cbw_stream_t stream);
 /* The encoder's self-attention (HF WhisperAttention under src/model/cb_whisper.py:100-104, non-causal, head dim
  * 64): qkv bf16 [B][T][3][H][64] with q pre-scaled by 1/8 -> out bf16 [B][T][H * 64], softmax in fp32. */
 int cbw_encoder_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int H, cbw_stream_t stream);

@@ -848,22 +848,25 @@ def test_decode_step_dev_graph_replay_bit_exact(name, rows):
         assert torch.equal(a, b), f"graph replay differs from the eager step at position {p}"
 
 
-def test_step_rows_windows_match_single_window_steps():
+@pytest.mark.parametrize("W,nb", [(3, 5), (2, 4), (4, 4)])
+def test_step_rows_windows_match_single_window_steps(W, nb):
     """cbw_decoder_step_rows: three windows' beams (3 x 5 = 15 rows, large-v3 widths: the 16-row GEMV instantiations --
     eight computing waves per workgroup, fc2's rows staged in two K halves) in one step, each window on its own encoder
     slot and at its own position
     (prefixes of 5, 12 and 73 tokens: self-attention within the first key chunk, and past the 64-key boundary),
     with a beam reorder inside each window, give every row the logits a step over its window alone gives, bit for
-    bit (cbw_decoder_cross_kv_slot + cbw_decoder_prefill_rows vs cbw_decoder_cross_kv + cbw_decoder_prefill)."""
+    bit (cbw_decoder_cross_kv_slot + cbw_decoder_prefill_rows vs cbw_decoder_cross_kv + cbw_decoder_prefill).
+    (2, 4) and (4, 4): 8 and 16 rows against 4-row steps, the row counts at which fc2 (K 5120) once left the dot
+    kernel for the MFMA kernel and the batched step's bits were not the single window's."""
     from cbw.decoder import DecoderEngine
     cfg = synth.WHISPER_DECODERS["large-v3-2l"]
     sd = synth.synth_whisper_decoder_state_dict("large-v3-2l", seed=0)
     g = torch.Generator(device="cuda").manual_seed(21)
-    W, nb, n_steps = 3, 5, 6
+    n_steps = 6
     encs = [torch.randn((1, 1500, cfg[1]), generator=g, device="cuda") for _ in range(W)]
-    prefixes = [[50258, 50259, 50360] + [400 + 7 * i for i in range(n)] for n in (2, 9, 70)]
+    prefixes = [[50258, 50259, 50360] + [400 + 7 * i for i in range(n)] for n in (2, 9, 70, 33)[:W]]
     toks = np.random.default_rng(5).integers(0, 50000, (n_steps, W * nb))
-    perm = [1, 1, 0, 4, 2]
+    perm = [1, 1, 0, 4, 2] if nb == 5 else [1, 1, 0, 3]
     ref = []
     for w in range(W):
         e = DecoderEngine(cfg, sd)
