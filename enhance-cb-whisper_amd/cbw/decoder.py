@@ -373,6 +373,105 @@ class DecoderEngine:
                             retire(w)
         return results
 
+    def greedy_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], eos: int, max_lengths,
+                       bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules=None,
+                       check_every: int = 8, return_logprobs: bool = False, max_slots: int = 16) -> List:
+        """Greedy search (HF 4.37.2 greedy branch of GenerationMixin.generate, the call of pba_whisper.py:318-331 and
+        :425-442 with num_beams = 1, do_sample = False) for several windows in lock step with no host round trip per
+        token: windows = [(enc_out f32 [1500, D] post-LN, decoder prefix)], max_lengths one per window (or one int),
+        decoded on one decoder state of min(len(windows), 16, ``max_slots``) slots of one row each, built as
+        beam_search_windows builds its slots.  Per step one cbw_greedy_select over all rows (scores = logits + ``bias_begin`` at a window's
+        first free position, ``bias`` after it, + the timestamp rules of ``rules`` from a device-side state; argmax;
+        log-prob of the processed scores) writes the step's row of a device log, cbw_decoder_step_rows reads its tokens
+        from there, and the rows still active move one position.  Every ``check_every`` steps the new log rows come
+        back in one copy and cbw.generate.greedy_replay reads them: finished windows leave, pending ones take their
+        slots; steps enqueued past a row's end are ignored (cbw_greedy_select's invariant keeps them inside the
+        cache).  Begin suppression and the rules' begin index are len(prefix); no forced positions.
+        Returns the sequences (prefix included) in window order; with ``return_logprobs`` (sequence, per-step
+        log-probs) pairs."""
+        from .generate import greedy_replay
+        n = len(windows)
+        limits = [int(max_lengths)] * n if isinstance(max_lengths, int) else [int(m) for m in max_lengths]
+        if len(limits) != n:
+            raise ValueError("greedy_windows needs one max_length per window")
+        if any(m > self.max_len for m in limits):
+            raise ValueError(f"max_length {max(limits)} exceeds the decoder's {self.max_len} positions")
+        if any(len(p) < 2 for _, p in windows):
+            raise ValueError("greedy_windows needs prefixes of >= 2 tokens")
+        check_every = max(1, int(check_every))
+        results: List = [None] * n
+        pending = []
+        for i, (_, p) in enumerate(windows):   # nothing to decode: `greedy` returns the prefix
+            if len(p) >= limits[i]:
+                results[i] = (list(p), []) if return_logprobs else list(p)
+            else:
+                pending.append(i)
+        if not pending:
+            return results
+        dev, stream = self.device, _lib.stream_handle()
+        tb, no_ts, max_initial = (rules.timestamp_begin, rules.no_timestamps, rules.max_initial) if rules is not None \
+            else (-1, -1, -1)
+        with torch.cuda.device(dev):
+            slots = max(1, min(len(pending), 16, int(max_slots)))
+            self.start_windows(slots, 1)
+            ts_state = torch.zeros((slots, 4), dtype=torch.int32, device=dev)
+            limit = torch.zeros((slots,), dtype=torch.int32, device=dev)
+            active = torch.zeros((slots,), dtype=torch.int32, device=dev)
+            # the log: per step one row of {tokens, log-probs (f32 bits), active} x slots, so a replay is one copy
+            log = torch.zeros((check_every, 3, slots), dtype=torch.int32, device=dev)
+            log_lp = log.view(torch.float32)
+            live: List[Optional[int]] = [None] * slots   # the window in each slot
+            seqs: List[Optional[List[int]]] = [None] * slots
+            lps: List[List[float]] = [[] for _ in range(slots)]
+            while pending or any(w is not None for w in live):
+                for slot in range(slots):
+                    if live[slot] is None and pending:
+                        i = pending.pop(0)
+                        enc_out, prefix = windows[i]
+                        self.set_window(slot, enc_out)
+                        self.prefill_window(slot, 1, prefix)
+                        ts_state[slot] = torch.tensor([0, -1, -1, -1], dtype=torch.int32)
+                        limit[slot:slot + 1].fill_(limits[i])
+                        active[slot:slot + 1].fill_(1)
+                        live[slot], seqs[slot], lps[slot] = i, list(prefix), []
+                # no row needs more steps than the longest remainder; the step after the last of those is not run
+                left = max(limits[w] - len(seqs[s]) for s, w in enumerate(live) if w is not None)
+                steps = min(check_every, left)
+                for c in range(steps):
+                    _lib.check(self.lib.cbw_greedy_select(self._logits.data_ptr(), slots, self.vocab, self.vpad,
+                                                          _lib.ptr(bias), _lib.ptr(bias_begin), tb, no_ts, eos,
+                                                          max_initial, ts_state.data_ptr(), self._posr.data_ptr(),
+                                                          limit.data_ptr(), active.data_ptr(), log[c, 0].data_ptr(),
+                                                          log_lp[c, 1].data_ptr(), stream), "cbw_greedy_select")
+                    log[c, 2].copy_(active)
+                    if c + 1 == left:
+                        break
+                    self.step_rows(log[c, 0])
+                    self._posr.add_(active)
+                host = log[:steps].cpu()   # the one device -> host copy (and sync) per check_every steps
+                toks, lpv, act = host[:, 0].numpy(), host[:, 1].view(torch.float32).numpy(), host[:, 2].numpy()
+                limits_s = [limits[w] if w is not None else 0 for w in live]
+                for slot, rep in enumerate(greedy_replay(toks, lpv, seqs, limits_s, eos)):
+                    if rep is None:
+                        continue
+                    seq, new_lps, finished = rep
+                    if bool(act[steps - 1, slot]) == finished:
+                        raise RuntimeError("GPU greedy bookkeeping diverged from the host replay")
+                    seqs[slot] = seq
+                    lps[slot] += new_lps
+                    if finished:
+                        results[live[slot]] = (seq, lps[slot]) if return_logprobs else seq
+                        live[slot], seqs[slot], lps[slot] = None, None, []
+        return results
+
+    def greedy_dev(self, enc_out: torch.Tensor, prefix: Sequence[int], eos: int, max_length: int,
+                   bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules=None, check_every: int = 8,
+                   return_logprobs: bool = False):
+        """greedy_windows over one window: enc_out f32 [1500, D] (or [1, 1500, D]) -> the sequence, or with
+        ``return_logprobs`` (sequence, per-step log-probs)."""
+        return self.greedy_windows([(enc_out, prefix)], eos, [max_length], bias, bias_begin, rules, check_every,
+                                   return_logprobs)[0]
+
     def sample_search(self, prefix: Sequence[int], eos: int, max_length: int, bias_at: callable, rules=None,
                       begin_index: int = 0, temperature: float = 0.0, top_k: int = 50,
                       generator: Optional[torch.Generator] = None, forced: Optional[dict] = None,

@@ -205,6 +205,42 @@ def greedy(step_fn: StepFn, prefix: Sequence[int], eos: int, max_length: int,
     return seq
 
 
+def greedy_select_state(ts_state: Sequence[int], token: int, pos: int, limit: int, eos: int,
+                        timestamp_begin: int = -1) -> Tuple[List[int], int]:
+    """The bookkeeping cbw_greedy_select does for one active row after it chose ``token`` for position ``pos``:
+    ts_state {n, last, second last, last timestamp} advanced by the token (``timestamp_begin`` < 0: no timestamp
+    rules, the last timestamp stays) and active = token != eos and pos + 1 < limit."""
+    n, t1, _, lts = (int(v) for v in ts_state)
+    if timestamp_begin >= 0 and token >= timestamp_begin:
+        lts = int(token)
+    return [n + 1, int(token), t1, lts], int(token != eos and pos + 1 < limit)
+
+
+def greedy_replay(tokens, logprobs, seqs: Sequence[Optional[Sequence[int]]], limits: Sequence[int], eos: int):
+    """The host's reading of a greedy device log (DecoderEngine.greedy_windows): tokens / logprobs [steps][rows], one
+    row per lock-step decode step as cbw_greedy_select wrote it; seqs[r] = row r's sequence before the first logged
+    step (the decoder prefix, or what earlier replays returned; None: no window in that row), limits[r] its
+    max_length.  A row takes the logged tokens in step order until it holds ``limits[r]`` tokens or took ``eos``, as
+    ``greedy`` ends; what is logged after that (the steps enqueued past its end) is ignored.
+    -> per row (sequence, log-probs of the tokens taken here, finished) or None."""
+    out = []
+    for r, seq in enumerate(seqs):
+        if seq is None:
+            out.append(None)
+            continue
+        seq, lps = [int(t) for t in seq], []
+        finished = len(seq) >= limits[r]
+        for s in range(len(tokens)):
+            if finished:
+                break
+            tok = int(tokens[s][r])
+            seq.append(tok)
+            lps.append(float(logprobs[s][r]))
+            finished = tok == eos or len(seq) >= limits[r]
+        out.append((seq, lps, finished))
+    return out
+
+
 def beam_sample(scores_fn, prefix: Sequence[int], num_beams: int, eos: int, max_length: int, temperature: float,
                 generator=None, top_k: int = 50, length_penalty: float = 1.0, decoder_prompt_len: int = 1,
                 return_score: bool = False, trace: Optional[list] = None, warp_order: str = "4.37"):

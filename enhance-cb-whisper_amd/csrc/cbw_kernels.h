@@ -290,6 +290,10 @@ hipError_t cbw_dec_gather_rows(const uint16_t* src, uint16_t* dst, const int* ro
 hipError_t cbw_beam_select_launch(const float* lp, const int* idx, int B, int k, int eos, double* beam_scores,
                                   double* cand_score, int* cand_row, int* cand_tok, int* tokens, int* parents, int* ok,
                                   int* ts_state, int* st_out, int ts_begin, int count, hipStream_t st);
+hipError_t cbw_greedy_select_launch(const float* logits, int B, int V, int ld, const float* bias,
+                                    const float* bias_begin, int ts_begin, int no_ts, int eos, int max_initial,
+                                    int* ts_state, const int* pos_rows, const int* limit, int* active, int* tokens,
+                                    float* logprob, hipStream_t st);
 hipError_t cbw_logprob_topk_launch(const float* logits, int B, int V, int ld, const float* bias, int64_t bias_ld,
                                    int k, float* lp, int* idx, hipStream_t st);
 hipError_t cbw_timestamp_rules_launch(const float* logits, int B, int V, int ld, const float* bias, const int* state,

@@ -3134,6 +3134,19 @@ int cbw_timestamp_rules(const float* logits, int B, int V, int ld, const float* 
     return CBW_OK;
 }
 
+int cbw_greedy_select(const float* logits, int B, int V, int ld, const float* bias, const float* bias_begin,
+                      int timestamp_begin, int no_timestamps, int eos, int max_initial, int32_t* ts_state,
+                      const int32_t* pos_rows, const int32_t* limit, int32_t* active, int32_t* tokens, float* logprob,
+                      cbw_stream_t stream) {
+    if (!logits || !ts_state || !pos_rows || !limit || !active || !tokens || !logprob || B < 1 || B > 16 || V < 1 ||
+        ld < V)
+        return fail(CBW_ERR_INVALID, "bad arguments (B in [1, 16], ld >= V >= 1)");
+    HIPCHK(cbw_greedy_select_launch(logits, B, V, ld, bias, bias_begin, timestamp_begin, no_timestamps, eos,
+                                    max_initial, ts_state, pos_rows, limit, active, tokens, logprob,
+                                    (hipStream_t)stream));
+    return CBW_OK;
+}
+
 // ------------------------------------------------------------------ building block
 }  // extern "C"
 namespace {

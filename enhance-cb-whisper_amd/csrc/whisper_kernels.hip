@@ -1073,6 +1073,145 @@ __global__ __launch_bounds__(1024) void timestamp_rules_kernel(const float* __re
         }
     }
 }
+
+// One greedy step's choice for every row of a lock-step decode, no host in the loop (HF 4.37.2 greedy search: the
+// processors on the raw logits, argmax, log_softmax of the processed scores for the fallback checks).  One block per
+// row, two passes over the row's V logits, eight loads in flight per thread in each:
+//   scores = logits + (n == 0 ? bias_begin : bias) + the masks timestamp_rules_kernel applies, its rule state derived
+//   here from ts_state[r] = {n, last, second last, last timestamp} as the end of beam_select_kernel derives it
+//   (ts_begin < 0: no timestamp rules); pass 1 the max and lowest argmax of the text and of the timestamp scores,
+//   pass 2 their sums of exponentials -> the mass rule (logsumexp of the timestamp scores > max text score: every
+//   text token masked), token = argmax of what is left (ties -> lower id), logprob = score - logsumexp(left).
+// Nothing finite left: token eos, logprob -inf.  Then ts_state[r] advances by the token and
+// active[r] = token != eos && pos_rows[r] + 1 < limit[r]; the driver adds active to pos_rows after the decode step.
+// A row inactive on entry only gets tokens[r] = eos.
+// Invariant the driver relies on: an active row steps at pos <= limit - 2 (its token was kept only if
+// pos + 1 < limit) and a row that ends stays at pos <= limit - 1 (it was selected at pos <= limit - 1 and its position
+// no longer moves), so every K/V write of the steps enqueued past a row's end stays below limit <= max_len.
+__global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __restrict__ logits, int V, int ld,
+                                                             const float* __restrict__ bias,
+                                                             const float* __restrict__ bias_begin, int ts_begin,
+                                                             int no_ts, int eos, int max_initial, int* ts_state,
+                                                             const int* __restrict__ pos_rows,
+                                                             const int* __restrict__ limit, int* active,
+                                                             int* __restrict__ tokens, float* __restrict__ logprob) {
+    __shared__ float red[16];
+    __shared__ int redi[16];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (!active[r]) {   // the whole block: uniform, before any barrier
+        if (tid == 0) tokens[r] = eos;
+        return;
+    }
+    const float* x = logits + (int64_t)r * ld;
+    const int sn = ts_state[4 * r], t1 = ts_state[4 * r + 1], t2 = ts_state[4 * r + 2], lts = ts_state[4 * r + 3];
+    const float* bs = sn == 0 ? bias_begin : bias;
+    const bool rules = ts_begin >= 0;
+    const int tb = rules ? ts_begin : V;   // text below, timestamps from tb on; rules off: every token is text
+    const bool last_ts = sn >= 1 && t1 >= tb, penult_ts = sn < 2 || t2 >= tb, at_begin = sn == 0;
+    const int ts_floor = lts < 0 ? tb : ((last_ts && !penult_ts) ? lts : lts + 1);
+    auto masked = [&](int i) -> bool {
+        bool m = i == no_ts;
+        if (last_ts) m = m || (penult_ts ? i >= tb : i < eos);
+        m = m || (i >= tb && i < ts_floor);
+        if (at_begin) m = m || i < tb || (max_initial >= 0 && i > tb + max_initial);
+        return rules && m;
+    };
+    // (max, lowest index of it) over the block; nothing above -inf: index 0x7fffffff
+    auto block_argmax = [&](float v, int i, float& M, int& I) {
+        const float wm = wave_max(v);
+        int ci = v == wm ? i : 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ci = min(ci, __shfl_xor(ci, o, 64));
+        if (lane == 0) { red[wid] = wm; redi[wid] = ci; }
+        __syncthreads();
+        M = red[0];
+        I = redi[0];
+        for (int w = 1; w < 16; ++w)
+            if (red[w] > M || (red[w] == M && redi[w] < I)) { M = red[w]; I = redi[w]; }
+        __syncthreads();
+    };
+    auto block_sum = [&](float v) -> float {
+        v = wave_sum(v);
+        if (lane == 0) red[wid] = v;
+        __syncthreads();
+        float tot = 0.f;
+        for (int w = 0; w < 16; ++w) tot += red[w];
+        __syncthreads();
+        return tot;
+    };
+    // unconditional loads of clamped indices, as timestamp_rules_kernel; a thread walks its indices in ascending
+    // order, so `>` keeps the lowest index of its maximum
+    const float* bsrc = bs ? bs : x;
+    float mt = -INFINITY, mts = -INFINITY;
+    int it = 0x7fffffff, its = 0x7fffffff;
+    for (int i0 = tid; i0 < V; i0 += 8 * 1024) {
+        float xv[8], bv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int ii = min(i0 + u * 1024, V - 1);
+            xv[u] = x[ii];
+            bv[u] = bsrc[ii];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * 1024;
+            if (i >= V) break;
+            const float v = masked(i) ? -INFINITY : xv[u] + (bs ? bv[u] : 0.f);
+            if (i < tb) {
+                if (v > mt) { mt = v; it = i; }
+            } else if (v > mts) {
+                mts = v;
+                its = i;
+            }
+        }
+    }
+    float m_text, m_ts;
+    int i_text, i_ts;
+    block_argmax(mt, it, m_text, i_text);
+    block_argmax(mts, its, m_ts, i_ts);
+    float st = 0.f, sts = 0.f;
+    for (int i0 = tid; i0 < V; i0 += 8 * 1024) {
+        float xv[8], bv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int ii = min(i0 + u * 1024, V - 1);
+            xv[u] = x[ii];
+            bv[u] = bsrc[ii];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * 1024;
+            if (i >= V) break;
+            const float v = masked(i) ? -INFINITY : xv[u] + (bs ? bv[u] : 0.f);
+            if (i < tb) st += m_text > -INFINITY ? __expf(v - m_text) : 0.f;
+            else sts += m_ts > -INFINITY ? __expf(v - m_ts) : 0.f;
+        }
+    }
+    const float s_text = block_sum(st), s_ts = block_sum(sts);
+    if (tid != 0) return;
+    const float lse_ts = m_ts > -INFINITY ? m_ts + logf(s_ts) : -INFINITY;
+    const bool force_ts = lse_ts > m_text;
+    const bool pick_ts = force_ts || m_ts > m_text;   // a tie across the boundary goes to the text token, the lower id
+    const float best = pick_ts ? m_ts : m_text;
+    int tok = pick_ts ? i_ts : i_text;
+    float lp = -INFINITY;
+    if (best > -INFINITY) {
+        const float M = fmaxf(m_text, m_ts);
+        const float lse = force_ts ? lse_ts
+                                   : M + logf((m_text > -INFINITY ? s_text * __expf(m_text - M) : 0.f) +
+                                              (m_ts > -INFINITY ? s_ts * __expf(m_ts - M) : 0.f));
+        lp = best - lse;
+    } else {
+        tok = eos;
+    }
+    ts_state[4 * r] = sn + 1;
+    ts_state[4 * r + 1] = tok;
+    ts_state[4 * r + 2] = t1;
+    if (rules && tok >= ts_begin) ts_state[4 * r + 3] = tok;
+    active[r] = (tok != eos && pos_rows[r] + 1 < limit[r]) ? 1 : 0;
+    tokens[r] = tok;
+    logprob[r] = lp;
+}
 }  // namespace
 
 hipError_t cbw_dec_embed(const int* tok, const uint16_t* E, const float* P, int pos, float* h, int B, int D,
@@ -1298,6 +1437,16 @@ hipError_t cbw_timestamp_rules_launch(const float* logits, int B, int V, int ld,
                                       hipStream_t st) {
     hipLaunchKernelGGL(timestamp_rules_kernel, dim3(B), dim3(1024), 0, st, logits, V, ld, bias, state, ts_begin, no_ts,
                        eos, max_initial, bias_out);
+    return hipGetLastError();
+}
+
+hipError_t cbw_greedy_select_launch(const float* logits, int B, int V, int ld, const float* bias,
+                                    const float* bias_begin, int ts_begin, int no_ts, int eos, int max_initial,
+                                    int* ts_state, const int* pos_rows, const int* limit, int* active, int* tokens,
+                                    float* logprob, hipStream_t st) {
+    if (B < 1 || B > 16 || V < 1 || ld < V) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, logits, V, ld, bias, bias_begin, ts_begin,
+                       no_ts, eos, max_initial, ts_state, pos_rows, limit, active, tokens, logprob);
     return hipGetLastError();
 }
 

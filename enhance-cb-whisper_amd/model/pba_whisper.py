@@ -41,6 +41,12 @@ from cbw.whisper import EncoderEngine
 N_FRAMES = 3000
 
 
+def _dev_greedy() -> bool:
+    """CBW_DEV_GREEDY, read at call time: greedy search with the token choice on the GPU (DecoderEngine.greedy_dev /
+    greedy_windows) instead of the host loop over step_fn; 0 switches it off."""
+    return os.environ.get("CBW_DEV_GREEDY", "1") != "0"
+
+
 def shortform_prefix(prompt: Sequence[int], init: Sequence[int], max_target_positions: int = 448) -> List[int]:
     """The forced decoder prefix of a short-form window with a keyword prompt, as transformers 4.37.2
     (requirements.txt:21) WhisperGenerationMixin._set_forced_decoder_ids builds it for pba_whisper.py:287-296: the
@@ -187,8 +193,13 @@ class PBAWhisper:
         bias_at = lambda pos: bias_begin if pos == begin_pos else bias   # noqa: E731
         rows = max(1, num_beams)
         rules = self.rules if timestamps else None
-        self.decoder.start(enc_out, rows)
         c = self._controls
+        if num_beams <= 1 and not free and c.get("repetition_penalty") is None and not c.get("no_repeat_ngram_size") \
+                and len(prefix) >= 2 and _dev_greedy():
+            # the token choice on the GPU, no host round trip per token (cbw_greedy_select; same result as `greedy`
+            # below); the cross-attention K/V go through set_window, so no decoder.start
+            return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin, rules)
+        self.decoder.start(enc_out, rows)
         lp, nrs = c.get("length_penalty", 1.0), c.get("num_return_sequences", 1)
         if c.get("repetition_penalty") is not None or c.get("no_repeat_ngram_size"):
             # a caller's multiplicative / n-gram processors: scores formed with torch ops on the device logits
@@ -235,6 +246,9 @@ class PBAWhisper:
         begin_pos = free["begin"] if free else len(prefix)
         bias, bias_begin = self._biases()
         bias_at = lambda pos: bias_begin if pos == begin_pos else bias   # noqa: E731
+        if not (temperature and temperature > 0) and not free and len(prefix) >= 2 and _dev_greedy():
+            return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin,
+                                           self.rules if timestamps else None, return_logprobs=True)
         self.decoder.start(enc_out, 1)
         return self.decoder.sample_search(prefix, self.tokens.eot, max_length, bias_at,
                                           self.rules if timestamps else None, begin_pos, temperature or 0.0,
@@ -612,6 +626,10 @@ class PBAWhisper:
                                                         self.tokens.eot, max_length, bias_at,
                                                         self.rules if timestamps else None, begin, begin,
                                                         length_penalty=self._controls.get("length_penalty", 1.0))
+            if num_beams <= 1 and len(segs) > 1 and all(len(p) >= 2 for p in prefixes) and _dev_greedy():
+                return self.decoder.greedy_windows([(enc[i], prefixes[i]) for i in range(len(segs))], self.tokens.eot,
+                                                   [self._window_max_length(len(p), max_new_tokens) for p in prefixes],
+                                                   bias, bias_begin, self.rules if timestamps else None)
             return [self.decode_window(enc[i:i + 1], prefixes[i], num_beams, max_new_tokens, timestamps=timestamps,
                                        decoder_prompt_len=begin) for i in range(len(segs))]
 

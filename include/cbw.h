@@ -433,6 +433,25 @@ int cbw_beam_select(const float* lp, const int32_t* idx, int B, int k, int eos, 
                     int32_t* ok, int32_t* ts_state, int32_t* st_out, int timestamp_begin, int count,
                     cbw_stream_t stream);
 
+/* One greedy-search step's choice for up to 16 rows on the GPU, so a greedy decode loop needs no host round trip
+ * per token (replaces the greedy branch of GenerationMixin.generate, num_beams = 1 and do_sample = False, reached
+ * from pba_whisper.py:318-331 short-form and :425-442 long-form, temperature 0 of the fallback included): per active
+ * row r, scores = logits[r] (f32, row pitch ld) + the shared bias (bias_begin [V] when the row has sampled nothing
+ * yet, ts_state[r][0] == 0, else bias [V]; either may be NULL) + WhisperTimeStampLogitsProcessor's masks as
+ * cbw_timestamp_rules applies them, the rule state derived from ts_state[r] (cbw_beam_select's {n, last, second last,
+ * last timestamp (-1)}); timestamp_begin < 0 switches the rules off.  No [B][V] bias is written or read.
+ * tokens[r] = argmax of the scores (ties -> lower id, as cbw_logprob_topk), logprob[r] = log_softmax(scores)[token]
+ * (HF applies the processors to the raw logits, then normalises); a row with nothing finite left gets eos and -inf.
+ * ts_state[r] advances by the token; active[r] = token != eos && pos_rows[r] + 1 < limit[r] (device int32 [B] each:
+ * the position the token goes to, the row's max_length) -- also the increment the caller adds to pos_rows after the
+ * decode step.  A row with active[r] == 0 on entry only gets tokens[r] = eos.  An active row therefore steps at
+ * pos <= limit - 2 and an ended row stays at pos <= limit - 1: cbw_decoder_step_rows over all rows stays below
+ * max_len for limit <= max_len.  Does not allocate or synchronise.  B in [1, 16], V >= 1, ld >= V. */
+int cbw_greedy_select(const float* logits, int B, int V, int ld, const float* bias, const float* bias_begin,
+                      int timestamp_begin, int no_timestamps, int eos, int max_initial, int32_t* ts_state,
+                      const int32_t* pos_rows, const int32_t* limit, int32_t* active, int32_t* tokens, float* logprob,
+                      cbw_stream_t stream);
+
 /* ---------------------------------------------------------------- building blocks (tests, tools)
  * NHWC bf16 implicit-GEMM convolution, y = act(conv(x, w) + bias (+ res)).
  * x [N][H][W][Cin], w [Cout][KH][KW][Cin], res/y [N][Ho][Wo][Cout]; Cin % 64 == 0, Cout % 64 == 0.
