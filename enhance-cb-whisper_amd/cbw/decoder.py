@@ -543,19 +543,11 @@ class DecoderEngine:
             self.step([prefix[0]], 0)
         return float(torch.softmax(self._logits[0, :self.vocab].double(), -1)[no_speech_token])
 
-    def scores_fn(self, bias_at: callable, rules=None, begin_index: int = 0):
-        """A cbw.generate.beam_sample scores function: reorder the KV cache, run one step, return every row's
-        processed log-probs for the next position as a device tensor [rows, V]: log_softmax(logits) + the
-        suppression bias (bias_at(pos)) and, with ``rules``, the per-row timestamp rules over each row's tokens since
-        ``begin_index`` (the masks step_fn's top-k sees)."""
+    def _stepper(self, scores: callable):
+        """The step function scores_fn, processed_step_fn and step_fn share: fn(tokens, pos, reorder_rows) reorders the
+        KV cache, tracks every row's sequence so far, runs one step and returns ``scores(pos + 1, seqs)``; fn.prefill
+        (Benc = 1) runs the forced prefix in one pass and returns the scores for position len(prefix)."""
         seqs = []
-
-        def scores(pos):
-            b = bias_at(pos)
-            lp = torch.log_softmax(self._logits[:, :self.vocab].float(), dim=-1)
-            if rules is not None and pos >= begin_index:
-                return lp + self.timestamp_bias(rules, [s[begin_index:] for s in seqs], b)
-            return lp + b if b is not None else lp
 
         def fn(tokens, pos, reorder_rows):
             nonlocal seqs
@@ -567,7 +559,7 @@ class DecoderEngine:
             for r, t in enumerate(tokens):
                 seqs[r].append(int(t))
             self.step(tokens, pos)
-            return scores(pos + 1)
+            return scores(pos + 1, seqs)
 
         def prefill(prefix):
             nonlocal seqs
@@ -575,9 +567,24 @@ class DecoderEngine:
                 return None
             seqs = [list(prefix) for _ in range(self._shape[0])]
             self.prefill(prefix)
-            return scores(len(prefix))
+            return scores(len(prefix), seqs)
         fn.prefill = prefill
         return fn
+
+    def scores_fn(self, bias_at: callable, rules=None, begin_index: int = 0):
+        """A cbw.generate.beam_sample scores function: reorder the KV cache, run one step, return every row's
+        processed log-probs for the next position as a device tensor [rows, V]: log_softmax(logits) + the
+        suppression bias (bias_at(pos)) and, with ``rules``, the per-row timestamp rules over each row's tokens since
+        ``begin_index`` (the masks step_fn's top-k sees)."""
+
+        def scores(pos, seqs):
+            b = bias_at(pos)
+            lp = torch.log_softmax(self._logits[:, :self.vocab].float(), dim=-1)
+            if rules is not None and pos >= begin_index:
+                return lp + self.timestamp_bias(rules, [s[begin_index:] for s in seqs], b)
+            return lp + b if b is not None else lp
+
+        return self._stepper(scores)
 
     def processed_step_fn(self, k: int, bias_at: callable, repetition_penalty: Optional[float] = None,
                           no_repeat_ngram_size: int = 0, greedy: bool = False):
@@ -587,10 +594,9 @@ class DecoderEngine:
         to each.  Each row's token history is the row's sequence so far (decoder prompt included).  The penalty is
         multiplicative, so the scores are formed with torch ops on the device logits and the top-k by a stable sort
         (ties -> lower id, as cbw_logprob_topk); no timestamp rules (the caller raises for that combination)."""
-        seqs = []
         V = self.vocab
 
-        def scores(pos):
+        def scores(pos, seqs):
             x = self._logits[:, :V].float()
             x = x.clone() if greedy else torch.log_softmax(x, dim=-1)
             for r, sq in enumerate(seqs):
@@ -607,27 +613,7 @@ class DecoderEngine:
             v, i = torch.sort(x, dim=-1, descending=True, stable=True)
             return v[:, :k].cpu().numpy(), i[:, :k].to(torch.int32).cpu().numpy()
 
-        def fn(tokens, pos, reorder_rows):
-            nonlocal seqs
-            if pos == 0:
-                seqs = [[] for _ in tokens]
-            if reorder_rows is not None:
-                self.reorder(reorder_rows, pos)
-                seqs = [list(seqs[r]) for r in reorder_rows]
-            for r, t in enumerate(tokens):
-                seqs[r].append(int(t))
-            self.step(tokens, pos)
-            return scores(pos + 1)
-
-        def prefill(prefix):
-            nonlocal seqs
-            if self._shape[1] != 1:
-                return None
-            seqs = [list(prefix) for _ in range(self._shape[0])]
-            self.prefill(prefix)
-            return scores(len(prefix))
-        fn.prefill = prefill
-        return fn
+        return self._stepper(scores)
 
     def step_fn(self, k: int, bias_at: callable, rules=None, begin_index: int = 0, free_pos: Optional[int] = None):
         """A cbw.generate StepFn: reorder the KV cache, run one step, return the top-k of
@@ -635,21 +621,8 @@ class DecoderEngine:
         (bias_at(pos) -> tensor or None) and, with ``rules`` (cbw.timestamps.TimestampRules), the
         per-row timestamp rules over each row's tokens since ``begin_index``; at ``free_pos`` (the free language
         position of short-form ``language=None``, before ``begin_index``) the rules in ``free_position_state``."""
-        seqs = []
 
-        def fn(tokens, pos, reorder_rows):
-            nonlocal seqs
-            if pos == 0:
-                seqs = [[] for _ in tokens]
-            if reorder_rows is not None:
-                self.reorder(reorder_rows, pos)
-                seqs = [list(seqs[r]) for r in reorder_rows]
-            for r, t in enumerate(tokens):
-                seqs[r].append(int(t))
-            self.step(tokens, pos)
-            return scores(pos + 1)
-
-        def scores(pos):
+        def scores(pos, seqs):
             b = bias_at(pos)
             if rules is not None and pos == free_pos:
                 return self.topk(k, self.timestamp_bias(rules, None, b, [free_position_state(rules)] * len(seqs)),
@@ -658,16 +631,7 @@ class DecoderEngine:
                 return self.topk(k, b)
             return self.topk(k, self.timestamp_bias(rules, [s[begin_index:] for s in seqs], b), self.vocab)
 
-        def prefill(prefix):
-            """the forced prefix in one pass (Benc = 1): scores for position len(prefix)"""
-            nonlocal seqs
-            if self._shape[1] != 1:
-                return None
-            seqs = [list(prefix) for _ in range(self._shape[0])]
-            self.prefill(prefix)
-            return scores(len(prefix))
-        fn.prefill = prefill
-        return fn
+        return self._stepper(scores)
 
 
 def banned_ngram_tokens(seq: Sequence[int], n: int) -> List[int]:

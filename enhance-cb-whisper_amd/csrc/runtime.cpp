@@ -244,14 +244,26 @@ struct Src2 {   // second K-source of a fused 1x1 conv (ConvArgs::x2)
 // output extent of a k-tap, "same"-padded (k / 2) conv or pool over h; k = 1: a strided 1x1 (the shortcuts)
 int out_dim(int h, int k, int stride) { return (h + 2 * (k / 2) - k) / stride + 1; }
 
-// the geometry fields ConvArgs, F32ConvArgs and F8ConvArgs share, for conv c over x [N][H][W][c.cin]
+// the geometry fields ConvArgs, F32ConvArgs and F8ConvArgs share, for a KH x KW conv over x [N][H][W][Cin]
+template <class Args>
+void conv_geometry(Args& a, int N, int H, int W, int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw) {
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
+    a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
+    a.Ho = (H + 2 * ph - KH) / sh + 1;
+    a.Wo = (W + 2 * pw - KW) / sw + 1;
+    a.M = N * a.Ho * a.Wo;
+}
+// ... for the square, "same"-padded conv c (out_dim's extents)
 template <class Args>
 void conv_geometry(Args& a, const ConvShape& c, int N, int H, int W) {
-    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout; a.KH = a.KW = c.k;
-    a.sh = a.sw = c.stride; a.ph = a.pw = c.k / 2;
-    a.Ho = out_dim(H, c.k, c.stride);
-    a.Wo = out_dim(W, c.k, c.stride);
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, N, H, W, c.cin, c.cout, c.k, c.k, c.stride, c.stride, c.k / 2, c.k / 2);
+}
+// the plain GEMM y[M][N] = x[M][K] . w[N][K]^T as a 1x1 conv over one row of M pixels (operands left to the caller)
+ConvArgs linear_args(int M, int K, int N) {
+    ConvArgs a{};
+    conv_geometry(a, 1, 1, M, K, N, 1, 1, 1, 1, 0, 0);
+    a.res_ld = a.y_ld = N;
+    return a;
 }
 
 int launch_conv(const ConvW& c, const void* x, int N, int H, int W, void* y, const void* res, int flags,
@@ -547,6 +559,16 @@ struct cbw_kws {
     }
 };
 
+struct LNorm {
+    DevBuf g, b;
+};
+// the fields a pre-LN Whisper layer has in the encoder and the decoder alike: self-attention (ln1 -> fused qkv ->
+// attention -> out) and MLP (ln_mlp -> fc1 + GELU -> fc2), each added to the fp32 residual stream
+struct XfLayer {
+    LNorm ln1, ln_mlp;
+    ConvW qkv, out, fc1, fc2;
+};
+
 struct cbw_encoder {
     cbw_encoder_config cfg{};
     ParamStore ps;
@@ -555,12 +577,8 @@ struct cbw_encoder {
     DevBuf zero;
     ConvW conv1, conv2;
     DevBuf pos;
-    struct Layer {
-        DevBuf ln1_g, ln1_b, ln2_g, ln2_b;
-        ConvW qkv, out, fc1, fc2;
-    };
-    std::vector<Layer> layers;
-    DevBuf lnf_g, lnf_b;
+    std::vector<XfLayer> layers;
+    LNorm lnf;
 };
 
 namespace {
@@ -2418,6 +2436,7 @@ int cbw_encoder_set_param(cbw_encoder* h, const char* name, const float* host, i
     return h->ps.set(name, host, numel);
 }
 
+}  // extern "C"
 namespace {
 int upload_vec(const ParamStore& ps, const std::string& n, size_t numel, DevBuf& dst) {
     int rc;
@@ -2442,66 +2461,144 @@ int upload_linear(const ParamStore& ps, const std::string& n, int cout, int cin,
     }
     return c.b.upload(b);
 }
+int upload_ln(const ParamStore& ps, const std::string& n, int D, LNorm& ln) {
+    CHK(upload_vec(ps, n + ".weight", D, ln.g));
+    return upload_vec(ps, n + ".bias", D, ln.b);
+}
+// fused QKV [3D][D] of attention block `p`: q (scaled by hd^-1/2, HF WhisperAttention.scaling) | k (no bias) | v
+int pack_qkv(const ParamStore& ps, const std::string& p, int D, ConvW& c) {
+    const float qscale = 1.0f / std::sqrt(64.0f);
+    int rc;
+    const auto* wq = ps.get(p + ".q_proj.weight", (size_t)D * D, &rc); if (!wq) return rc;
+    const auto* wk = ps.get(p + ".k_proj.weight", (size_t)D * D, &rc); if (!wk) return rc;
+    const auto* wv = ps.get(p + ".v_proj.weight", (size_t)D * D, &rc); if (!wv) return rc;
+    const auto* bq = ps.get(p + ".q_proj.bias", D, &rc); if (!bq) return rc;
+    const auto* bv = ps.get(p + ".v_proj.bias", D, &rc); if (!bv) return rc;
+    std::vector<float> w((size_t)3 * D * D), b((size_t)3 * D, 0.f);
+    for (size_t j = 0; j < (size_t)D * D; ++j) {
+        w[j] = (*wq)[j] * qscale;
+        w[(size_t)D * D + j] = (*wk)[j];
+        w[(size_t)2 * D * D + j] = (*wv)[j];
+    }
+    for (int j = 0; j < D; ++j) { b[j] = (*bq)[j] * qscale; b[2 * D + j] = (*bv)[j]; }
+    c.cin = D; c.cout = 3 * D; c.k = 1;
+    CHK(c.w.upload(to_bf16(w)));
+    return c.b.upload(b);
+}
+// the fields of layer `p` ("layers.<i>") that the encoder and the decoder share
+int load_xf_layer(const ParamStore& ps, const std::string& p, int D, int F, XfLayer& L) {
+    CHK(upload_ln(ps, p + ".self_attn_layer_norm", D, L.ln1));
+    CHK(pack_qkv(ps, p + ".self_attn", D, L.qkv));
+    CHK(upload_linear(ps, p + ".self_attn.out_proj", D, D, true, L.out));
+    CHK(upload_ln(ps, p + ".final_layer_norm", D, L.ln_mlp));
+    CHK(upload_linear(ps, p + ".fc1", F, D, true, L.fc1));
+    return upload_linear(ps, p + ".fc2", D, F, true, L.fc2);
+}
+
+// the K/V cache append of a decode step's qkv projection: k / v = the layer's cache at position 0 (row stride ld
+// elements), written at position pos, or at the position(s) read on the device from pos_dev (GemvArgs::kv_pos)
+struct KvAppend {
+    uint16_t *k = nullptr, *v = nullptr;
+    int64_t ld = 0;
+    int D = 0, pos = 0;
+    const int32_t* pos_dev = nullptr;
+    int pos_rows = 0;
+};
+// The one place a GemvArgs is filled: y[M][N] = act(x . w^T + bias (+ res)) over bf16 rows x, or with xf over
+// LN(xf) (the LayerNorm prologue); kv_k (optional): the output's K and V thirds also go to the cache rows kv_k / kv_v
+GemvArgs gemv_args(const uint16_t* x, const float* xf, int ldx, const float* ln_g, const float* ln_b, float ln_eps,
+                   const void* w, const float* bias, const void* res, int res_ld, void* y, int ldy, int M, int N, int K,
+                   int flags, uint16_t* kv_k = nullptr, uint16_t* kv_v = nullptr, int64_t kv_ld = 0, int kv_D = 0,
+                   const int32_t* kv_pos = nullptr, int kv_pos_rows = 0) {
+    GemvArgs a{};
+    a.x = xf ? nullptr : (const bf16*)x; a.ldx = ldx; a.w = (const bf16*)w; a.bias = bias;
+    a.res = res; a.res_ld = res_ld; a.y = y; a.ldy = ldy;
+    a.M = M; a.N = N; a.K = K; a.flags = flags;
+    a.xf = xf; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
+    if (kv_k) {
+        a.kv_k = (bf16*)kv_k; a.kv_v = (bf16*)kv_v; a.kv_ld = kv_ld; a.kv_D = kv_D;
+        a.kv_pos = kv_pos; a.kv_pos_rows = kv_pos_rows;
+    }
+    return a;
+}
+
+// The Linears of one encoder / decoder entry call, all over M rows on stream st: on the skinny GEMV (gemv.hip) where
+// gemv is set (<= 16 rows, CBW_DEC_GEMV), else on the implicit-GEMM tiles; with fuse a LayerNorm in front of a Linear
+// runs in the GEMV's prologue (and the K/V append in its epilogue), else as launches of their own (LayerNorm into the
+// bf16 rows ln_out).  The knobs are read once per entry call, by whoever builds the LinearRun.
+struct LinearRun {
+    int M;
+    hipStream_t st;
+    const void* zero;
+    bool gemv, fuse;
+    uint16_t* ln_out;
+    float* splitk = nullptr;   // the encoder's split-K partial sums, for its residual Linears (out-projection, fc2)
+
+    int lin(const ConvW& c, const void* x, void* y, const void* res, int flags) const {
+        if (!gemv) return launch_conv(c, x, 1, 1, M, y, res, flags, zero, st, nullptr, nullptr, res ? splitk : nullptr);
+        return run(c, (const uint16_t*)x, nullptr, nullptr, y, res, flags, KvAppend{});
+    }
+    int ln_lin(const float* h32, const LNorm& ln, const ConvW& c, void* y, int flags, const KvAppend& kv = {}) const {
+        if (fuse) return run(c, nullptr, h32, &ln, y, nullptr, flags, kv);
+        HIPCHK(cbw_layernorm(h32, ln.g.as<float>(), ln.b.as<float>(), ln_out, nullptr, M, c.cin, 1e-5f, st));
+        CHK(lin(c, ln_out, y, nullptr, flags));
+        if (kv.k) HIPCHK(cbw_dec_kv_append((const uint16_t*)y, kv.k, kv.v, M, kv.D, (int)(kv.ld / kv.D), kv.pos, st));
+        return CBW_OK;
+    }
+    int add_lin(const ConvW& c, const void* x, float* h) const {   // residual Linear of the fp32 stream: h += c(x)
+        return lin(c, x, h, h, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32);
+    }
+    int run(const ConvW& c, const uint16_t* x, const float* xf, const LNorm* ln, void* y, const void* res, int flags,
+            const KvAppend& kv) const {
+        const size_t at = kv.pos_dev ? 0 : (size_t)kv.pos * kv.D;
+        const GemvArgs g = gemv_args(x, xf, c.cin, ln ? ln->g.as<float>() : nullptr, ln ? ln->b.as<float>() : nullptr,
+                                     ln ? 1e-5f : 0.f, c.w.p, c.b.as<float>(), res, res ? c.cout : 0, y, c.cout, M,
+                                     c.cout, c.cin, flags | (c.relu ? CBW_EPI_RELU : 0), kv.k ? kv.k + at : nullptr,
+                                     kv.k ? kv.v + at : nullptr, kv.ld, kv.D, kv.pos_dev, kv.pos_rows);
+        HIPCHK(cbw_gemv(g, st));
+        return CBW_OK;
+    }
+};
+
+// attention sub-block of a pre-LN layer: h += out(attend()), where attend reads q = proj(LN(h)) and writes att
+template <class Attend>
+int attn_block(const LinearRun& r, const LNorm& ln, const ConvW& proj, const ConvW& out, float* h, uint16_t* q,
+               const uint16_t* att, const KvAppend& kv, Attend&& attend) {
+    CHK(r.ln_lin(h, ln, proj, q, 0, kv));
+    CHK(attend());
+    return r.add_lin(out, att, h);
+}
+// MLP sub-block: h += fc2(gelu(fc1(LN(h)))), f = the fc1 rows
+int mlp_block(const LinearRun& r, const XfLayer& L, float* h, uint16_t* f) {
+    CHK(r.ln_lin(h, L.ln_mlp, L.fc1, f, CBW_EPI_GELU));
+    return r.add_lin(L.fc2, f, h);
+}
 }  // namespace
+extern "C" {
 
 int cbw_encoder_finalize(cbw_encoder* h) {
     if (!h) return fail(CBW_ERR_INVALID, "null handle");
     const int D = h->cfg.d_model, F = h->cfg.ffn_dim, nm = h->cfg.n_mel, cp = h->cpad;
-    int rc;
-    // conv1 [D][n_mel][3] -> [D][1][3][cpad]; conv2 [D][D][3] -> [D][1][3][D]
-    {
-        const auto* w = h->ps.get("conv1.weight", (size_t)D * nm * 3, &rc); if (!w) return rc;
-        std::vector<float> o((size_t)D * 3 * cp, 0.f);
+    // the stem's k3 convs, torch [D][cin][3] -> [D][1][3][cpad]: conv1 (n_mel in, padded to cpad), conv2 (D in)
+    auto load_k3 = [&](const std::string& n, int cin, int cpad, ConvW& c) -> int {
+        int rc;
+        const auto* w = h->ps.get(n + ".weight", (size_t)D * cin * 3, &rc); if (!w) return rc;
+        std::vector<float> o((size_t)D * 3 * cpad, 0.f);
         for (int co = 0; co < D; ++co)
-            for (int ci = 0; ci < nm; ++ci)
-                for (int k = 0; k < 3; ++k) o[((size_t)co * 3 + k) * cp + ci] = (*w)[((size_t)co * nm + ci) * 3 + k];
-        h->conv1.cin = cp; h->conv1.cout = D; h->conv1.k = 3;
-        CHK(h->conv1.w.upload(to_bf16(o)));
-        CHK(upload_vec(h->ps, "conv1.bias", D, h->conv1.b));
-        const auto* w2 = h->ps.get("conv2.weight", (size_t)D * D * 3, &rc); if (!w2) return rc;
-        std::vector<float> o2((size_t)D * 3 * D);
-        for (int co = 0; co < D; ++co)
-            for (int ci = 0; ci < D; ++ci)
-                for (int k = 0; k < 3; ++k) o2[((size_t)co * 3 + k) * D + ci] = (*w2)[((size_t)co * D + ci) * 3 + k];
-        h->conv2.cin = D; h->conv2.cout = D; h->conv2.k = 3;
-        CHK(h->conv2.w.upload(to_bf16(o2)));
-        CHK(upload_vec(h->ps, "conv2.bias", D, h->conv2.b));
-    }
+            for (int ci = 0; ci < cin; ++ci)
+                for (int k = 0; k < 3; ++k) o[((size_t)co * 3 + k) * cpad + ci] = (*w)[((size_t)co * cin + ci) * 3 + k];
+        c.cin = cpad; c.cout = D; c.k = 3;
+        CHK(c.w.upload(to_bf16(o)));
+        return upload_vec(h->ps, n + ".bias", D, c.b);
+    };
+    CHK(load_k3("conv1", nm, cp, h->conv1));
+    CHK(load_k3("conv2", D, D, h->conv2));
     CHK(upload_vec(h->ps, "embed_positions.weight", (size_t)1500 * D, h->pos));
     h->layers.clear();
     h->layers.resize(h->cfg.n_layers);
-    const float qscale = 1.0f / std::sqrt(64.0f);
-    for (int i = 0; i < h->cfg.n_layers; ++i) {
-        auto& L = h->layers[i];
-        const std::string p = "layers." + std::to_string(i);
-        CHK(upload_vec(h->ps, p + ".self_attn_layer_norm.weight", D, L.ln1_g));
-        CHK(upload_vec(h->ps, p + ".self_attn_layer_norm.bias", D, L.ln1_b));
-        CHK(upload_vec(h->ps, p + ".final_layer_norm.weight", D, L.ln2_g));
-        CHK(upload_vec(h->ps, p + ".final_layer_norm.bias", D, L.ln2_b));
-        // fused QKV [3D][D]: q (scaled by hd^-1/2, HF WhisperAttention.scaling) | k (no bias) | v
-        {
-            const auto* wq = h->ps.get(p + ".self_attn.q_proj.weight", (size_t)D * D, &rc); if (!wq) return rc;
-            const auto* wk = h->ps.get(p + ".self_attn.k_proj.weight", (size_t)D * D, &rc); if (!wk) return rc;
-            const auto* wv = h->ps.get(p + ".self_attn.v_proj.weight", (size_t)D * D, &rc); if (!wv) return rc;
-            const auto* bq = h->ps.get(p + ".self_attn.q_proj.bias", D, &rc); if (!bq) return rc;
-            const auto* bv = h->ps.get(p + ".self_attn.v_proj.bias", D, &rc); if (!bv) return rc;
-            std::vector<float> w((size_t)3 * D * D), b((size_t)3 * D, 0.f);
-            for (size_t j = 0; j < (size_t)D * D; ++j) {
-                w[j] = (*wq)[j] * qscale;
-                w[(size_t)D * D + j] = (*wk)[j];
-                w[(size_t)2 * D * D + j] = (*wv)[j];
-            }
-            for (int j = 0; j < D; ++j) { b[j] = (*bq)[j] * qscale; b[2 * D + j] = (*bv)[j]; }
-            L.qkv.cin = D; L.qkv.cout = 3 * D; L.qkv.k = 1;
-            CHK(L.qkv.w.upload(to_bf16(w)));
-            CHK(L.qkv.b.upload(b));
-        }
-        CHK(upload_linear(h->ps, p + ".self_attn.out_proj", D, D, true, L.out));
-        CHK(upload_linear(h->ps, p + ".fc1", F, D, true, L.fc1));
-        CHK(upload_linear(h->ps, p + ".fc2", D, F, true, L.fc2));
-    }
-    CHK(upload_vec(h->ps, "layer_norm.weight", D, h->lnf_g));
-    CHK(upload_vec(h->ps, "layer_norm.bias", D, h->lnf_b));
+    for (int i = 0; i < h->cfg.n_layers; ++i)
+        CHK(load_xf_layer(h->ps, "layers." + std::to_string(i), D, F, h->layers[i]));
+    CHK(upload_ln(h->ps, "layer_norm", D, h->lnf));
     h->finalized = true;
     return CBW_OK;
 }
@@ -2519,9 +2616,7 @@ int64_t encoder_splitk_floats(const cbw_encoder* h, int B) {
     const int D = h->cfg.d_model, F = h->cfg.ffn_dim, M = B * 1500;
     int64_t n = 0;
     for (int K : {D, F}) {
-        ConvArgs a{};
-        a.KH = a.KW = 1; a.Cin = K; a.Cout = D; a.M = M;
-        const int S = cbw_conv_splitk_factor(a);
+        const int S = cbw_conv_splitk_factor(linear_args(M, K, D));
         if (S > 1) n = std::max<int64_t>(n, (int64_t)S * M * D);
     }
     return n;
@@ -2567,44 +2662,36 @@ int cbw_encoder_hs(cbw_encoder* h, const uint16_t* mel, int B, const int32_t* la
         }
         return CBW_OK;
     };
-    // conv1 (k3, p1) + GELU: [B][1][3000][cpad] -> [B][1][3000][D]
-    {
-        ConvArgs c{};
-        c.x = mel; c.w = h->conv1.w.p; c.bias = h->conv1.b.as<float>(); c.y = x1; c.zero = h->zero.p;
-        c.N = B; c.H = 1; c.W = 3000; c.Cin = h->cpad; c.Cout = D; c.KH = 1; c.KW = 3;
-        c.sh = 1; c.sw = 1; c.ph = 0; c.pw = 1; c.Ho = 1; c.Wo = 3000; c.M = B * 3000; c.res_ld = c.y_ld = D;
-        c.flags = CBW_EPI_GELU;
-        HIPCHK(cbw_conv_igemm(c, st));
-    }
-    // conv2 (k3, s2, p1) + GELU + positions (per clip: the position table is [1500][D])
-    for (int b = 0; b < B; ++b) {
-        ConvArgs c{};
-        c.x = x1 + (size_t)b * 3000 * D; c.w = h->conv2.w.p; c.bias = h->conv2.b.as<float>(); c.res = h->pos.p;
-        c.y = hbuf + (size_t)b * T * D; c.zero = h->zero.p;
-        c.N = 1; c.H = 1; c.W = 3000; c.Cin = D; c.Cout = D; c.KH = 1; c.KW = 3;
-        c.sh = 1; c.sw = 2; c.ph = 0; c.pw = 1; c.Ho = 1; c.Wo = T; c.M = T; c.res_ld = c.y_ld = D;
-        c.flags = CBW_EPI_GELU | CBW_EPI_RES_F32 | CBW_EPI_OUT_F32 | CBW_EPI_RES_AFTER_ACT;
-        HIPCHK(cbw_conv_igemm(c, st));
-    }
+    // the stem's k3 convs (p1) over n clips of 3000 frames, + GELU
+    auto conv_k3 = [&](const ConvW& c, const void* x, const void* res, void* y, int n, int sw, int flags) {
+        ConvArgs a{};
+        a.x = x; a.w = c.w.p; a.bias = c.b.as<float>(); a.res = res; a.y = y; a.zero = h->zero.p;
+        conv_geometry(a, n, 1, 3000, c.cin, D, 1, 3, 1, sw, 0, 1);
+        a.res_ld = a.y_ld = D;
+        a.flags = CBW_EPI_GELU | flags;
+        return cbw_conv_igemm(a, st);
+    };
+    // conv1: [B][1][3000][cpad] -> [B][1][3000][D]; conv2 (s2) + positions (per clip: the position table is [1500][D])
+    HIPCHK(conv_k3(h->conv1, mel, nullptr, x1, B, 1, 0));
+    for (int b = 0; b < B; ++b)
+        HIPCHK(conv_k3(h->conv2, x1 + (size_t)b * 3000 * D, h->pos.p, hbuf + (size_t)b * T * D, 1, 2,
+                       CBW_EPI_RES_F32 | CBW_EPI_OUT_F32 | CBW_EPI_RES_AFTER_ACT));
     CHK(capture(0));
+    const LinearRun run{M, st, h->zero.p, false, false, a, part};
     for (int i = 0; i < last_layer && i < N; ++i) {
-        auto& L = h->layers[i];
-        HIPCHK(cbw_layernorm(hbuf, L.ln1_g.as<float>(), L.ln1_b.as<float>(), a, nullptr, M, D, 1e-5f, st));
-        CHK(launch_conv(L.qkv, a, 1, 1, M, qkv, nullptr, 0, h->zero.p, st));
-        HIPCHK(cbw_attention(qkv, att, B, T, H, 64, st));
-        CHK(launch_conv(L.out, att, 1, 1, M, hbuf, hbuf, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st, nullptr,
-                        nullptr, part));
-        HIPCHK(cbw_layernorm(hbuf, L.ln2_g.as<float>(), L.ln2_b.as<float>(), a, nullptr, M, D, 1e-5f, st));
-        CHK(launch_conv(L.fc1, a, 1, 1, M, f, nullptr, CBW_EPI_GELU, h->zero.p, st));
-        CHK(launch_conv(L.fc2, f, 1, 1, M, hbuf, hbuf, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st, nullptr,
-                        nullptr, part));
+        const XfLayer& L = h->layers[i];
+        CHK(attn_block(run, L.ln1, L.qkv, L.out, hbuf, qkv, att, {}, [&]() -> int {
+            HIPCHK(cbw_attention(qkv, att, B, T, H, 64, st));
+            return CBW_OK;
+        }));
+        CHK(mlp_block(run, L, hbuf, f));
         if (i + 1 < N) CHK(capture(i + 1));
     }
     if (last_layer >= N) {
         for (int j = 0; j < n_ids; ++j) {
             if (layer_ids[j] != N) continue;
             for (int b = 0; b < B; ++b)
-                HIPCHK(cbw_layernorm(hbuf + (size_t)b * T * D, h->lnf_g.as<float>(), h->lnf_b.as<float>(), nullptr,
+                HIPCHK(cbw_layernorm(hbuf + (size_t)b * T * D, h->lnf.g.as<float>(), h->lnf.b.as<float>(), nullptr,
                                      hs + (((size_t)b * n_ids + j) * T) * D, T, D, 1e-5f, st));
         }
     }
@@ -2621,13 +2708,14 @@ struct cbw_decoder {
     bool finalized = false;
     int Vpad = 0;
     DevBuf zero;
-    DevBuf emb, pos;
-    struct Layer {
-        DevBuf ln1_g, ln1_b, ln2_g, ln2_b, ln3_g, ln3_b;
-        ConvW qkv, out, cq, ck, cv, co, fc1, fc2;
+    ConvW emb;   // the padded token embedding [Vpad][D], also the tied vocabulary projection (a Linear without bias)
+    DevBuf pos;
+    struct Layer : XfLayer {   // + the cross-attention block
+        LNorm ln_x;
+        ConvW cq, ck, cv, co;
     };
     std::vector<Layer> layers;
-    DevBuf lnf_g, lnf_b;
+    LNorm lnf;
 };
 
 namespace {
@@ -2681,6 +2769,20 @@ DecState dec_carve(const cbw_decoder* h, void* state, int B, int Benc) {
 }
 int64_t dec_state_bytes(const cbw_decoder* h, int B, int Benc) {   // the carve of a state at address 0
     return (int64_t)(dec_carve(h, nullptr, B, Benc).end - (char*)nullptr);
+}
+// What every decoder compute entry checks first (ptrs_ok: its own pointer arguments): a finalized handle and B rows
+// that are a positive multiple of the Benc encoder slots.  The entry's own range checks come next, then dec_state.
+int dec_check(const cbw_decoder* h, bool ptrs_ok, int B, int Benc) {
+    if (!h || !ptrs_ok) return fail(CBW_ERR_INVALID, "null argument");
+    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_decoder_finalize not called");
+    if (B <= 0 || Benc <= 0 || B % Benc) return fail(CBW_ERR_INVALID, "B must be a positive multiple of Benc");
+    return CBW_OK;
+}
+// ... and last: the state's size, and its carve
+int dec_state(const cbw_decoder* h, void* state, int64_t state_bytes, int B, int Benc, DecState* s) {
+    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
+    *s = dec_carve(h, state, B, Benc);
+    return CBW_OK;
 }
 // the step's attention: split-key kernel (K/V read once per kv batch) when it applies, else one workgroup per row
 int dec_self_split_keys() {   // CBW_DEC_SELF_SPLIT=N: self-attention over more than N keys on the split kernel
@@ -2743,7 +2845,8 @@ int cbw_decoder_finalize(cbw_decoder* h) {
         if (!e) return rc;
         std::vector<float> ep((size_t)h->Vpad * D, 0.f);
         std::copy(e->begin(), e->end(), ep.begin());
-        CHK(h->emb.upload(to_bf16(ep)));
+        h->emb.cin = D; h->emb.cout = h->Vpad; h->emb.k = 1;
+        CHK(h->emb.w.upload(to_bf16(ep)));
         const auto* p = h->ps.get("embed_positions.weight", (size_t)448 * D, &rc);
         if (!p) return rc;
         CHK(h->pos.upload(*p));
@@ -2754,39 +2857,14 @@ int cbw_decoder_finalize(cbw_decoder* h) {
     for (int i = 0; i < h->cfg.n_layers; ++i) {
         auto& L = h->layers[i];
         const std::string p = "layers." + std::to_string(i);
-        CHK(upload_vec(h->ps, p + ".self_attn_layer_norm.weight", D, L.ln1_g));
-        CHK(upload_vec(h->ps, p + ".self_attn_layer_norm.bias", D, L.ln1_b));
-        CHK(upload_vec(h->ps, p + ".encoder_attn_layer_norm.weight", D, L.ln2_g));
-        CHK(upload_vec(h->ps, p + ".encoder_attn_layer_norm.bias", D, L.ln2_b));
-        CHK(upload_vec(h->ps, p + ".final_layer_norm.weight", D, L.ln3_g));
-        CHK(upload_vec(h->ps, p + ".final_layer_norm.bias", D, L.ln3_b));
-        {
-            const auto* wq = h->ps.get(p + ".self_attn.q_proj.weight", (size_t)D * D, &rc); if (!wq) return rc;
-            const auto* wk = h->ps.get(p + ".self_attn.k_proj.weight", (size_t)D * D, &rc); if (!wk) return rc;
-            const auto* wv = h->ps.get(p + ".self_attn.v_proj.weight", (size_t)D * D, &rc); if (!wv) return rc;
-            const auto* bq = h->ps.get(p + ".self_attn.q_proj.bias", D, &rc); if (!bq) return rc;
-            const auto* bv = h->ps.get(p + ".self_attn.v_proj.bias", D, &rc); if (!bv) return rc;
-            std::vector<float> w((size_t)3 * D * D), b((size_t)3 * D, 0.f);
-            for (size_t j = 0; j < (size_t)D * D; ++j) {
-                w[j] = (*wq)[j] * qscale;
-                w[(size_t)D * D + j] = (*wk)[j];
-                w[(size_t)2 * D * D + j] = (*wv)[j];
-            }
-            for (int j = 0; j < D; ++j) { b[j] = (*bq)[j] * qscale; b[2 * D + j] = (*bv)[j]; }
-            L.qkv.cin = D; L.qkv.cout = 3 * D; L.qkv.k = 1;
-            CHK(L.qkv.w.upload(to_bf16(w)));
-            CHK(L.qkv.b.upload(b));
-        }
-        CHK(upload_linear(h->ps, p + ".self_attn.out_proj", D, D, true, L.out));
+        CHK(load_xf_layer(h->ps, p, D, F, L));
+        CHK(upload_ln(h->ps, p + ".encoder_attn_layer_norm", D, L.ln_x));
         CHK(upload_linear(h->ps, p + ".encoder_attn.q_proj", D, D, true, L.cq, qscale));
         CHK(upload_linear(h->ps, p + ".encoder_attn.k_proj", D, D, false, L.ck));
         CHK(upload_linear(h->ps, p + ".encoder_attn.v_proj", D, D, true, L.cv));
         CHK(upload_linear(h->ps, p + ".encoder_attn.out_proj", D, D, true, L.co));
-        CHK(upload_linear(h->ps, p + ".fc1", F, D, true, L.fc1));
-        CHK(upload_linear(h->ps, p + ".fc2", D, F, true, L.fc2));
     }
-    CHK(upload_vec(h->ps, "layer_norm.weight", D, h->lnf_g));
-    CHK(upload_vec(h->ps, "layer_norm.bias", D, h->lnf_b));
+    CHK(upload_ln(h->ps, "layer_norm", D, h->lnf));
     h->finalized = true;
     return CBW_OK;
 }
@@ -2796,41 +2874,40 @@ int64_t cbw_decoder_state_bytes(cbw_decoder* h, int B, int Benc) {
     return dec_state_bytes(h, B, Benc);
 }
 
-int cbw_decoder_cross_kv(cbw_decoder* h, const float* enc_out, int Benc, void* state, int64_t state_bytes, int B,
-                         cbw_stream_t stream) {
-    if (!h || !enc_out || !state) return fail(CBW_ERR_INVALID, "null argument");
-    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_decoder_finalize not called");
-    if (B <= 0 || Benc <= 0 || B % Benc) return fail(CBW_ERR_INVALID, "B must be a positive multiple of Benc");
-    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+namespace {
+// cross-attention K/V of `rows` encoder rows (enc_out f32 [rows][D]) into every layer's cross cache, at element
+// offset `at` of the state's bf16 encoder copy and of each layer's [Benc x 1500][D] cache
+int dec_cross_kv(cbw_decoder* h, const float* enc_out, size_t at, int rows, int Benc, const DecState& s,
+                 hipStream_t st) {
     const int D = h->cfg.d_model;
-    DecState s = dec_carve(h, state, B, Benc);
-    HIPCHK(cbw_cast_permute_lbtd(enc_out, s.enc, 1, 1, Benc * 1500, D, st));
+    HIPCHK(cbw_cast_permute_lbtd(enc_out, s.enc + at, 1, 1, rows, D, st));
     const size_t per = (size_t)Benc * 1500 * D;
+    const LinearRun run{rows, st, h->zero.p, false, false, nullptr};
     for (int l = 0; l < h->cfg.n_layers; ++l) {
-        CHK(launch_conv(h->layers[l].ck, s.enc, 1, 1, Benc * 1500, s.kc + l * per, nullptr, 0, h->zero.p, st));
-        CHK(launch_conv(h->layers[l].cv, s.enc, 1, 1, Benc * 1500, s.vc + l * per, nullptr, 0, h->zero.p, st));
+        CHK(run.lin(h->layers[l].ck, s.enc + at, s.kc + l * per + at, nullptr, 0));
+        CHK(run.lin(h->layers[l].cv, s.enc + at, s.vc + l * per + at, nullptr, 0));
     }
     return CBW_OK;
+}
+}  // namespace
+extern "C" {
+
+int cbw_decoder_cross_kv(cbw_decoder* h, const float* enc_out, int Benc, void* state, int64_t state_bytes, int B,
+                         cbw_stream_t stream) {
+    CHK(dec_check(h, enc_out && state, B, Benc));
+    DecState s;
+    CHK(dec_state(h, state, state_bytes, B, Benc, &s));
+    return dec_cross_kv(h, enc_out, 0, Benc * 1500, Benc, s, (hipStream_t)stream);
 }
 
 int cbw_decoder_cross_kv_slot(cbw_decoder* h, const float* enc_out, int slot, int Benc, void* state,
                               int64_t state_bytes, int B, cbw_stream_t stream) {
-    if (!h || !enc_out || !state) return fail(CBW_ERR_INVALID, "null argument");
-    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_decoder_finalize not called");
-    if (B <= 0 || Benc <= 0 || B % Benc || slot < 0 || slot >= Benc)
-        return fail(CBW_ERR_INVALID, "B must be a positive multiple of Benc, 0 <= slot < Benc");
-    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int D = h->cfg.d_model;
-    DecState s = dec_carve(h, state, B, Benc);
-    const size_t per = (size_t)Benc * 1500 * D, at = (size_t)slot * 1500 * D;
-    HIPCHK(cbw_cast_permute_lbtd(enc_out, s.enc + at, 1, 1, 1500, D, st));
-    for (int l = 0; l < h->cfg.n_layers; ++l) {
-        CHK(launch_conv(h->layers[l].ck, s.enc + at, 1, 1, 1500, s.kc + l * per + at, nullptr, 0, h->zero.p, st));
-        CHK(launch_conv(h->layers[l].cv, s.enc + at, 1, 1, 1500, s.vc + l * per + at, nullptr, 0, h->zero.p, st));
-    }
-    return CBW_OK;
+    CHK(dec_check(h, enc_out && state, B, Benc));
+    if (slot < 0 || slot >= Benc) return fail(CBW_ERR_INVALID, "cross_kv_slot needs 0 <= slot < Benc");
+    DecState s;
+    CHK(dec_state(h, state, state_bytes, B, Benc, &s));
+    return dec_cross_kv(h, enc_out, (size_t)slot * 1500 * h->cfg.d_model, 1500, Benc, s, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -2840,89 +2917,41 @@ namespace {
 // holds one position per row (the rows of several windows, each at its own position, in one step)
 int dec_step(cbw_decoder* h, const int32_t* tokens, int pos, const int32_t* pos_dev, int B, int Benc, void* state,
              int64_t state_bytes, float* logits, cbw_stream_t stream, int pos_rows = 0) {
-    if (!h || !tokens || !state || !logits) return fail(CBW_ERR_INVALID, "null argument");
-    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_decoder_finalize not called");
-    if (B <= 0 || Benc <= 0 || B % Benc || (!pos_dev && (pos < 0 || pos >= h->cfg.max_len)))
-        return fail(CBW_ERR_INVALID, "bad B/Benc/pos");
-    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
+    CHK(dec_check(h, tokens && state && logits, B, Benc));
+    if (!pos_dev && (pos < 0 || pos >= h->cfg.max_len)) return fail(CBW_ERR_INVALID, "step needs 0 <= pos < max_len");
+    DecState s;
+    CHK(dec_state(h, state, state_bytes, B, Benc, &s));
     hipStream_t st = (hipStream_t)stream;
     const int D = h->cfg.d_model, H = h->cfg.n_heads, ML = h->cfg.max_len;
-    DecState s = dec_carve(h, state, B, Benc);
-    // the step's Linears: skinny GEMV (gemv.hip) for <= 16 rows, else the implicit-GEMM tiles
+    // the step's Linears: skinny GEMV (gemv.hip) for <= 16 rows, else the implicit-GEMM tiles; LayerNorm -> Linear
+    // pairs: on the GEMV the LayerNorm runs in its prologue (and the qkv projection appends K/V to the cache in its
+    // epilogue), else as separate launches
     const bool gemv = dec_gemv_enabled(B);
-    auto lin = [&](const ConvW& c, const void* x, void* y, const void* res, int flags) -> int {
-        if (!gemv) return launch_conv(c, x, 1, 1, B, y, res, flags, h->zero.p, st);
-        GemvArgs g{};
-        g.x = (const bf16*)x; g.ldx = c.cin; g.w = c.w.as<bf16>(); g.bias = c.b.as<float>();
-        g.res = res; g.res_ld = c.cout; g.y = y; g.ldy = c.cout;
-        g.M = B; g.N = c.cout; g.K = c.cin; g.flags = flags | (c.relu ? CBW_EPI_RELU : 0);
-        HIPCHK(cbw_gemv(g, st));
-        return CBW_OK;
-    };
-    // LayerNorm -> Linear pairs: on the GEMV the LayerNorm runs in its prologue (and the qkv projection
-    // appends K/V to the cache in its epilogue), else as separate launches
-    const bool fuse = gemv && dec_fuse_enabled() && cbw_gemv_ln_ok(B, D);
-    if (pos_dev && !fuse)
+    const LinearRun run{B, st, h->zero.p, gemv, gemv && dec_fuse_enabled() && cbw_gemv_ln_ok(B, D), s.a};
+    if (pos_dev && !run.fuse)
         return fail(CBW_ERR_INVALID, "device-position steps need the fused GEMV path (<= 16 rows, CBW_DEC_GEMV / "
                                      "CBW_DEC_FUSE on)");
-    auto ln_lin = [&](const DevBuf& g, const DevBuf& b, const ConvW& c, void* y, int flags, uint16_t* kk,
-                      uint16_t* vv) -> int {
-        if (!fuse) {
-            HIPCHK(cbw_layernorm(s.h, g.as<float>(), b.as<float>(), s.a, nullptr, B, D, 1e-5f, st));
-            CHK(lin(c, s.a, y, nullptr, flags));
-            if (kk) HIPCHK(cbw_dec_kv_append((const uint16_t*)y, kk, vv, B, D, ML, pos, st));
-            return CBW_OK;
-        }
-        GemvArgs a{};
-        a.xf = s.h; a.ldx = D; a.ln_g = g.as<float>(); a.ln_b = b.as<float>(); a.ln_eps = 1e-5f;
-        a.w = c.w.as<bf16>(); a.bias = c.b.as<float>(); a.y = y; a.ldy = c.cout;
-        a.M = B; a.N = c.cout; a.K = c.cin; a.flags = flags | (c.relu ? CBW_EPI_RELU : 0);
-        if (kk) {
-            a.kv_k = (bf16*)kk + (pos_dev ? 0 : (size_t)pos * D); a.kv_v = (bf16*)vv + (pos_dev ? 0 : (size_t)pos * D);
-            a.kv_ld = (int64_t)ML * D; a.kv_D = D; a.kv_pos = pos_dev; a.kv_pos_rows = pos_rows;
-        }
-        HIPCHK(cbw_gemv(a, st));
-        return CBW_OK;
-    };
-    HIPCHK(cbw_dec_embed(tokens, h->emb.as<uint16_t>(), h->pos.as<float>(), pos, s.h, B, D, st, 0, pos_dev, pos_rows));
+    HIPCHK(cbw_dec_embed(tokens, h->emb.w.as<uint16_t>(), h->pos.as<float>(), pos, s.h, B, D, st, 0, pos_dev, pos_rows));
     const size_t self_per = (size_t)B * ML * D, cross_per = (size_t)Benc * 1500 * D;
     for (int l = 0; l < h->cfg.n_layers; ++l) {
         auto& L = h->layers[l];
         uint16_t* kl = s.ks + l * self_per;
         uint16_t* vl = s.vs + l * self_per;
-        CHK(ln_lin(L.ln1_g, L.ln1_b, L.qkv, s.qkv, 0, kl, vl));
-        HIPCHK(dec_attend(s, s.qkv, 3 * D, kl, vl, (int64_t)ML * D, pos_dev ? ML : pos + 1, 1, s.att, B, H, D, st,
-                          pos_dev, true, pos_rows));
-        CHK(lin(L.out, s.att, s.h, s.h, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32));
-        CHK(ln_lin(L.ln2_g, L.ln2_b, L.cq, s.qc, 0, nullptr, nullptr));
-        HIPCHK(dec_attend(s, s.qc, D, s.kc + l * cross_per, s.vc + l * cross_per, (int64_t)1500 * D, 1500, B / Benc,
-                          s.att, B, H, D, st));
-        CHK(lin(L.co, s.att, s.h, s.h, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32));
-        CHK(ln_lin(L.ln3_g, L.ln3_b, L.fc1, s.f, CBW_EPI_GELU, nullptr, nullptr));
-        CHK(lin(L.fc2, s.f, s.h, s.h, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32));
+        const KvAppend kv{kl, vl, (int64_t)ML * D, D, pos, pos_dev, pos_rows};
+        CHK(attn_block(run, L.ln1, L.qkv, L.out, s.h, s.qkv, s.att, kv, [&]() -> int {
+            HIPCHK(dec_attend(s, s.qkv, 3 * D, kl, vl, (int64_t)ML * D, pos_dev ? ML : pos + 1, 1, s.att, B, H, D, st,
+                              pos_dev, true, pos_rows));
+            return CBW_OK;
+        }));
+        CHK(attn_block(run, L.ln_x, L.cq, L.co, s.h, s.qc, s.att, {}, [&]() -> int {
+            HIPCHK(dec_attend(s, s.qc, D, s.kc + l * cross_per, s.vc + l * cross_per, (int64_t)1500 * D, 1500,
+                              B / Benc, s.att, B, H, D, st));
+            return CBW_OK;
+        }));
+        CHK(mlp_block(run, L, s.h, s.f));
     }
-    if (fuse) {   // final LayerNorm in the vocabulary projection's prologue
-        GemvArgs g{};
-        g.xf = s.h; g.ldx = D; g.ln_g = h->lnf_g.as<float>(); g.ln_b = h->lnf_b.as<float>(); g.ln_eps = 1e-5f;
-        g.w = h->emb.as<bf16>(); g.y = logits; g.ldy = h->Vpad;
-        g.M = B; g.N = h->Vpad; g.K = D; g.flags = CBW_EPI_OUT_F32;
-        HIPCHK(cbw_gemv(g, st));
-        return CBW_OK;
-    }
-    HIPCHK(cbw_layernorm(s.h, h->lnf_g.as<float>(), h->lnf_b.as<float>(), s.a, nullptr, B, D, 1e-5f, st));
-    ConvArgs c{};
-    c.x = s.a; c.w = h->emb.p; c.bias = nullptr; c.res = nullptr; c.y = logits; c.zero = h->zero.p;
-    c.N = 1; c.H = 1; c.W = B; c.Cin = D; c.Cout = h->Vpad; c.KH = 1; c.KW = 1; c.sh = c.sw = 1; c.ph = c.pw = 0;
-    c.Ho = 1; c.Wo = B; c.M = B; c.res_ld = c.y_ld = h->Vpad; c.flags = CBW_EPI_OUT_F32;
-    if (gemv) {   // vocabulary projection
-        GemvArgs g{};
-        g.x = (const bf16*)s.a; g.ldx = D; g.w = h->emb.as<bf16>(); g.y = logits; g.ldy = h->Vpad;
-        g.M = B; g.N = h->Vpad; g.K = D; g.flags = CBW_EPI_OUT_F32;
-        HIPCHK(cbw_gemv(g, st));
-    } else {
-        HIPCHK(cbw_conv_igemm(c, st));
-    }
-    return CBW_OK;
+    // the final LayerNorm and the tied vocabulary projection
+    return run.ln_lin(s.h, h->lnf, h->emb, logits, CBW_EPI_OUT_F32);
 }
 
 }  // namespace
@@ -2954,40 +2983,37 @@ int cbw_decoder_prefill(cbw_decoder* h, const int32_t* tokens, int T, int B, int
 }  // extern "C"
 
 namespace {
-// The prefill layers: the T tokens as rows at positions 0..T-1, their K/V into cache rows [r0, r0 + nb) (attending to
-// encoder slot `slot`); s.ph ends as the last layer's residual stream.  probes (n_probe > 0): right after layer l's
-// cross-attention query, the probabilities of each listed (layer, head) pair of that layer -> probs[i] [T][1500].
+// The prefill layers: the T prefix tokens as T rows at positions 0..T-1 (the beams are identical through a forced
+// prefix: one row set), their K/V replicated into cache rows [r0, r0 + nb), which attend to encoder slot `slot`; s.ph
+// ends as the last layer's residual stream.  probes (n_probe > 0): right after layer l's cross-attention query, the
+// probabilities of each listed (layer, head) pair of that layer -> probs[i] [T][1500].
 int dec_prefill_layers(cbw_decoder* h, const int32_t* tokens, int T, int slot, int r0, int nb, int B, int Benc,
                        const DecState& s, hipStream_t st, const int32_t* probe = nullptr, int n_probe = 0,
                        float* probs = nullptr) {
     const int D = h->cfg.d_model, H = h->cfg.n_heads, ML = h->cfg.max_len;
-    // the T prefix tokens as T rows at positions 0..T-1 (the beams are identical through a forced prefix:
-    // one row set, its K/V replicated into every beam row of the cache: rows r0 .. r0 + nb - 1, which attend to
-    // encoder slot `slot`)
-    HIPCHK(cbw_dec_embed(tokens, h->emb.as<uint16_t>(), h->pos.as<float>(), 0, s.ph, T, D, st, 1));
+    const LinearRun run{T, st, h->zero.p, false, false, s.pa};
+    HIPCHK(cbw_dec_embed(tokens, h->emb.w.as<uint16_t>(), h->pos.as<float>(), 0, s.ph, T, D, st, 1));
     const size_t self_per = (size_t)B * ML * D, cross_per = (size_t)Benc * 1500 * D;
     for (int l = 0; l < h->cfg.n_layers; ++l) {
         auto& L = h->layers[l];
         uint16_t* kl = s.ks + l * self_per + (size_t)r0 * ML * D;
         uint16_t* vl = s.vs + l * self_per + (size_t)r0 * ML * D;
-        HIPCHK(cbw_layernorm(s.ph, L.ln1_g.as<float>(), L.ln1_b.as<float>(), s.pa, nullptr, T, D, 1e-5f, st));
-        CHK(launch_conv(L.qkv, s.pa, 1, 1, T, s.pqkv, nullptr, 0, h->zero.p, st));
-        HIPCHK(cbw_dec_kv_prefill(s.pqkv, kl, vl, T, nb, D, ML, st));
-        HIPCHK(cbw_dec_attention(s.pqkv, 3 * D, kl, vl, (int64_t)ML * D, T, T, s.patt, T, H, D, st, 1));
-        CHK(launch_conv(L.out, s.patt, 1, 1, T, s.ph, s.ph, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st));
-        HIPCHK(cbw_layernorm(s.ph, L.ln2_g.as<float>(), L.ln2_b.as<float>(), s.pa, nullptr, T, D, 1e-5f, st));
-        CHK(launch_conv(L.cq, s.pa, 1, 1, T, s.pqc, nullptr, 0, h->zero.p, st));
-        for (int i = 0; i < n_probe; ++i)
-            if (probe[2 * i] == l)
-                HIPCHK(cbw_dec_cross_probs(s.pqc, D, s.kc + l * cross_per + (size_t)slot * 1500 * D, 1500, T, D,
-                                           probe[2 * i + 1], probs + (size_t)i * T * 1500, st));
-        HIPCHK(cbw_dec_attention(s.pqc, D, s.kc + l * cross_per + (size_t)slot * 1500 * D,
-                                 s.vc + l * cross_per + (size_t)slot * 1500 * D, (int64_t)1500 * D, 1500, T,
-                                 s.patt, T, H, D, st));
-        CHK(launch_conv(L.co, s.patt, 1, 1, T, s.ph, s.ph, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st));
-        HIPCHK(cbw_layernorm(s.ph, L.ln3_g.as<float>(), L.ln3_b.as<float>(), s.pa, nullptr, T, D, 1e-5f, st));
-        CHK(launch_conv(L.fc1, s.pa, 1, 1, T, s.pf, nullptr, CBW_EPI_GELU, h->zero.p, st));
-        CHK(launch_conv(L.fc2, s.pf, 1, 1, T, s.ph, s.ph, CBW_EPI_RES_F32 | CBW_EPI_OUT_F32, h->zero.p, st));
+        const uint16_t* kx = s.kc + l * cross_per + (size_t)slot * 1500 * D;
+        const uint16_t* vx = s.vc + l * cross_per + (size_t)slot * 1500 * D;
+        CHK(attn_block(run, L.ln1, L.qkv, L.out, s.ph, s.pqkv, s.patt, {}, [&]() -> int {
+            HIPCHK(cbw_dec_kv_prefill(s.pqkv, kl, vl, T, nb, D, ML, st));
+            HIPCHK(cbw_dec_attention(s.pqkv, 3 * D, kl, vl, (int64_t)ML * D, T, T, s.patt, T, H, D, st, 1));
+            return CBW_OK;
+        }));
+        CHK(attn_block(run, L.ln_x, L.cq, L.co, s.ph, s.pqc, s.patt, {}, [&]() -> int {
+            for (int i = 0; i < n_probe; ++i)
+                if (probe[2 * i] == l)
+                    HIPCHK(cbw_dec_cross_probs(s.pqc, D, kx, 1500, T, D, probe[2 * i + 1], probs + (size_t)i * T * 1500,
+                                               st));
+            HIPCHK(cbw_dec_attention(s.pqc, D, kx, vx, (int64_t)1500 * D, 1500, T, s.patt, T, H, D, st));
+            return CBW_OK;
+        }));
+        CHK(mlp_block(run, L, s.ph, s.pf));
     }
     return CBW_OK;
 }
@@ -2997,47 +3023,30 @@ extern "C" {
 
 int cbw_decoder_prefill_rows(cbw_decoder* h, const int32_t* tokens, int T, int slot, int r0, int nb, int B, int Benc,
                              void* state, int64_t state_bytes, float* logits, cbw_stream_t stream) {
-    if (!h || !tokens || !state || !logits) return fail(CBW_ERR_INVALID, "null argument");
-    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_decoder_finalize not called");
-    if (B < 1 || Benc < 1 || B % Benc || T < 1 || T > h->cfg.max_len || slot < 0 || slot >= Benc || nb < 1 || r0 < 0 ||
-        r0 + nb > B)
+    CHK(dec_check(h, tokens && state && logits, B, Benc));
+    if (T < 1 || T > h->cfg.max_len || slot < 0 || slot >= Benc || nb < 1 || r0 < 0 || r0 + nb > B)
         return fail(CBW_ERR_INVALID, "prefill needs 1 <= T <= max_len, 0 <= slot < Benc, rows [r0, r0 + nb) within B");
-    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
+    DecState s;
+    CHK(dec_state(h, state, state_bytes, B, Benc, &s));
     hipStream_t st = (hipStream_t)stream;
-    const int D = h->cfg.d_model;
-    DecState s = dec_carve(h, state, B, Benc);
     CHK(dec_prefill_layers(h, tokens, T, slot, r0, nb, B, Benc, s, st));
-    // logits of the last prefix token only
-    const float* last = s.ph + (size_t)(T - 1) * D;
-    HIPCHK(cbw_layernorm(last, h->lnf_g.as<float>(), h->lnf_b.as<float>(), s.pa, nullptr, 1, D, 1e-5f, st));
-    if (dec_gemv_enabled(B)) {   // the vocabulary projection on the same kernel as the step's
-        GemvArgs g{};
-        g.x = (const bf16*)s.pa; g.ldx = D; g.w = h->emb.as<bf16>(); g.y = logits; g.ldy = h->Vpad;
-        g.M = 1; g.N = h->Vpad; g.K = D; g.flags = CBW_EPI_OUT_F32;
-        HIPCHK(cbw_gemv(g, st));
-    } else {
-        ConvArgs c{};
-        c.x = s.pa; c.w = h->emb.p; c.y = logits; c.zero = h->zero.p;
-        c.N = 1; c.H = 1; c.W = 1; c.Cin = D; c.Cout = h->Vpad; c.KH = 1; c.KW = 1; c.sh = c.sw = 1;
-        c.Ho = 1; c.Wo = 1; c.M = 1; c.res_ld = c.y_ld = h->Vpad; c.flags = CBW_EPI_OUT_F32;
-        HIPCHK(cbw_conv_igemm(c, st));
-    }
-    return CBW_OK;
+    // logits of the last prefix token only: one row, its vocabulary projection on the same kernel as the step's
+    const LinearRun last{1, st, h->zero.p, dec_gemv_enabled(B), false, s.pa};
+    return last.ln_lin(s.ph + (size_t)(T - 1) * h->cfg.d_model, h->lnf, h->emb, logits, CBW_EPI_OUT_F32);
 }
 
 int cbw_decoder_cross_attn_probs(cbw_decoder* h, const int32_t* tokens, int T, const int32_t* heads, int n, int B,
                                  int Benc, void* state, int64_t state_bytes, float* probs, cbw_stream_t stream) {
-    if (!h || !tokens || !heads || !state || !probs) return fail(CBW_ERR_INVALID, "null argument");
-    if (!h->finalized) return fail(CBW_ERR_STATE, "cbw_decoder_finalize not called");
-    if (B < 1 || Benc < 1 || B % Benc || T < 1 || T > h->cfg.max_len || n < 1)
-        return fail(CBW_ERR_INVALID, "cross_attn_probs needs 1 <= T <= max_len, n >= 1, B a multiple of Benc");
+    CHK(dec_check(h, tokens && heads && state && probs, B, Benc));
+    if (T < 1 || T > h->cfg.max_len || n < 1)
+        return fail(CBW_ERR_INVALID, "cross_attn_probs needs 1 <= T <= max_len, n >= 1");
     if (h->cfg.d_model != 64 * h->cfg.n_heads) return fail(CBW_ERR_INVALID, "cross_attn_probs: head dim must be 64");
     for (int i = 0; i < n; ++i)
         if (heads[2 * i] < 0 || heads[2 * i] >= h->cfg.n_layers || heads[2 * i + 1] < 0 ||
             heads[2 * i + 1] >= h->cfg.n_heads)
             return fail(CBW_ERR_INVALID, "cross_attn_probs: (layer, head) out of range");
-    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
-    DecState s = dec_carve(h, state, B, Benc);
+    DecState s;
+    CHK(dec_state(h, state, state_bytes, B, Benc, &s));
     return dec_prefill_layers(h, tokens, T, 0, 0, 1, B, Benc, s, (hipStream_t)stream, heads, n, probs);
 }
 
@@ -3083,11 +3092,11 @@ int cbw_decoder_reorder(cbw_decoder* h, const int32_t* src_rows, int B, int Benc
                         int64_t state_bytes, cbw_stream_t stream) {
     if (!h || !src_rows || !state) return fail(CBW_ERR_INVALID, "null argument");
     if (B <= 0 || Benc <= 0 || B % Benc || len < 0 || len > h->cfg.max_len) return fail(CBW_ERR_INVALID, "bad arguments");
-    if (state_bytes < dec_state_bytes(h, B, Benc)) return fail(CBW_ERR_OOM, "decoder state too small");
+    DecState s;
+    CHK(dec_state(h, state, state_bytes, B, Benc, &s));
     if (len == 0) return CBW_OK;
     hipStream_t st = (hipStream_t)stream;
     const int D = h->cfg.d_model, ML = h->cfg.max_len;
-    DecState s = dec_carve(h, state, B, Benc);
     const size_t self_per = (size_t)B * ML * D;
     if (B <= 16) {   // every layer's K and V in one in-place launch
         HIPCHK(cbw_dec_reorder_kv(s.ks, s.vs, src_rows, B, h->cfg.n_layers, (int64_t)self_per, (int64_t)ML * D,
@@ -3176,11 +3185,7 @@ int cbw_conv2d(const uint16_t* x, const uint16_t* w, const float* bias, const vo
     CHK(block_zero_page(&zp));
     ConvArgs a{};
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y; a.zero = zp;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
-    a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
-    a.Ho = (H + 2 * ph - KH) / sh + 1;
-    a.Wo = (W + 2 * pw - KW) / sw + 1;
-    a.M = N * a.Ho * a.Wo;
+    conv_geometry(a, N, H, W, Cin, Cout, KH, KW, sh, sw, ph, pw);
     a.res_ld = a.y_ld = Cout;
     a.flags = flags;
     HIPCHK(cbw_conv_igemm(a, (hipStream_t)stream));
@@ -3195,9 +3200,7 @@ int cbw_conv1x1_chain(const uint16_t* x, const uint16_t* we, const float* be, co
     CHK(block_zero_page(&zp));
     ConvArgs a{};
     a.x = x; a.w = we; a.bias = be; a.res = res; a.y = y; a.zero = zp;
-    a.N = N; a.H = a.Ho = H; a.W = a.Wo = W; a.Cin = 128; a.Cout = 512; a.KH = a.KW = 1;
-    a.sh = a.sw = 1;
-    a.M = N * H * W;
+    conv_geometry(a, N, H, W, 128, 512, 1, 1, 1, 1, 0, 0);
     a.res_ld = a.y_ld = 512;
     a.flags = CBW_EPI_RELU;
     if (!cbw_conv_chain_supported(a, 128)) return fail(CBW_ERR_INVALID, "cbw_conv1x1_chain: shape not supported");
@@ -3211,9 +3214,7 @@ int cbw_conv1x1_chain(const uint16_t* x, const uint16_t* we, const float* be, co
 
 int cbw_gemm_splitk_factor(int M, int K, int N) {
     if (M <= 0 || K <= 0 || N <= 0) return fail(CBW_ERR_INVALID, "cbw_gemm_splitk_factor: bad shape");
-    ConvArgs a{};
-    a.KH = a.KW = 1; a.Cin = K; a.Cout = N; a.M = M;
-    return cbw_conv_splitk_factor(a);
+    return cbw_conv_splitk_factor(linear_args(M, K, N));
 }
 
 int cbw_encoder_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int H, cbw_stream_t stream) {
@@ -3228,11 +3229,8 @@ int cbw_gemm(const uint16_t* x, const uint16_t* w, const float* bias, const void
         return fail(CBW_ERR_INVALID, "cbw_gemm: K and N must be multiples of 64");
     const void* zp = nullptr;
     CHK(block_zero_page(&zp));
-    ConvArgs a{};
+    ConvArgs a = linear_args(M, K, N);
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y; a.zero = zp;
-    a.N = 1; a.H = 1; a.W = M; a.Cin = K; a.Cout = N; a.KH = a.KW = 1;
-    a.sh = a.sw = 1; a.ph = a.pw = 0; a.Ho = 1; a.Wo = M; a.M = M;
-    a.res_ld = a.y_ld = N;
     a.flags = flags;
     const int S = ksplit == 0 ? cbw_conv_splitk_factor(a) : ksplit;
     if (S > 1) {
@@ -3259,16 +3257,9 @@ int cbw_linear_rows(const uint16_t* x, const float* xf, int ldx, const float* ln
         return fail(CBW_ERR_INVALID, "cbw_linear_rows: K/V append needs kv_v, N == 3 kv_D, kv_D % 4, kv_ld % 4, bf16 output");
     if (gemv_route(M, N, K, xf != nullptr).kernel == GemvKernel::Invalid)
         return fail(CBW_ERR_INVALID, "cbw_linear_rows: no kernel for this shape");
-    GemvArgs a{};
-    a.x = xf ? nullptr : (const bf16*)x; a.ldx = ldx; a.w = (const bf16*)w; a.bias = bias;
-    a.res = res; a.res_ld = res_ld; a.y = y; a.ldy = ldy;
-    a.M = M; a.N = N; a.K = K; a.flags = flags;
-    a.xf = xf; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
-    if (kv_k) {
-        a.kv_k = (bf16*)kv_k; a.kv_v = (bf16*)kv_v; a.kv_ld = kv_ld; a.kv_D = kv_D;
-        a.kv_pos = kv_pos; a.kv_pos_rows = kv_pos_rows;
-    }
-    HIPCHK(cbw_gemv(a, (hipStream_t)stream));
+    HIPCHK(cbw_gemv(gemv_args(x, xf, ldx, ln_g, ln_b, ln_eps, w, bias, res, res_ld, y, ldy, M, N, K, flags, kv_k, kv_v,
+                              kv_ld, kv_D, kv_pos, kv_pos_rows),
+                    (hipStream_t)stream));
     return CBW_OK;
 }
 
@@ -3293,10 +3284,7 @@ int cbw_conv1x1_dual(const uint16_t* x, const uint16_t* x2, const uint16_t* w, c
     ConvArgs a{};
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y; a.zero = zp;
     a.x2 = x2; a.Cin2 = Cin2; a.H2 = H2; a.W2 = W2; a.s2 = s2;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = a.KW = 1;
-    a.sh = a.sw = 1; a.ph = a.pw = 0;
-    a.Ho = H; a.Wo = W;
-    a.M = N * H * W;
+    conv_geometry(a, N, H, W, Cin, Cout, 1, 1, 1, 1, 0, 0);
     a.res_ld = a.y_ld = Cout;
     a.flags = flags;
     HIPCHK(cbw_conv_igemm(a, (hipStream_t)stream));
