@@ -4,6 +4,7 @@ log-softmax + top-k with additive suppression bias.  Drives cbw.generate."""
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -389,15 +390,28 @@ class DecoderEngine:
         cache).  Begin suppression and the rules' begin index are len(prefix); no forced positions.
         Returns the sequences (prefix included) in window order; with ``return_logprobs`` (sequence, per-step
         log-probs) pairs."""
+        def select(args, live, stream):
+            _lib.check(self.lib.cbw_greedy_select(*args, stream), "cbw_greedy_select")
+        return self._lock_step("greedy_windows", windows, eos, max_lengths, bias, bias_begin, rules, select,
+                               check_every, return_logprobs, max_slots)
+
+    def _lock_step(self, name: str, windows, eos: int, max_lengths, bias, bias_begin, rules, select: callable,
+                   check_every: int, return_logprobs: bool, max_slots: int, replayed: Optional[callable] = None) -> List:
+        """The lock-step driver greedy_windows and sample_windows share: slot admission, the device log of
+        ``check_every`` steps, the one copy per replay, cbw.generate.greedy_replay and the divergence check.  Per step
+        ``select(args, live, stream)`` makes the rows' choice: ``args`` are the arguments cbw_greedy_select and
+        cbw_sample_select have in common (logits ... logprob, writing the step's row of the log), ``live[slot]`` the
+        window in each slot (None: empty).  ``replayed(window, taken, finished)`` is called after every replay with the
+        number of logged steps the window took from it."""
         from .generate import greedy_replay
         n = len(windows)
         limits = [int(max_lengths)] * n if isinstance(max_lengths, int) else [int(m) for m in max_lengths]
         if len(limits) != n:
-            raise ValueError("greedy_windows needs one max_length per window")
+            raise ValueError(f"{name} needs one max_length per window")
         if any(m > self.max_len for m in limits):
             raise ValueError(f"max_length {max(limits)} exceeds the decoder's {self.max_len} positions")
         if any(len(p) < 2 for _, p in windows):
-            raise ValueError("greedy_windows needs prefixes of >= 2 tokens")
+            raise ValueError(f"{name} needs prefixes of >= 2 tokens")
         check_every = max(1, int(check_every))
         results: List = [None] * n
         pending = []
@@ -438,11 +452,9 @@ class DecoderEngine:
                 left = max(limits[w] - len(seqs[s]) for s, w in enumerate(live) if w is not None)
                 steps = min(check_every, left)
                 for c in range(steps):
-                    _lib.check(self.lib.cbw_greedy_select(self._logits.data_ptr(), slots, self.vocab, self.vpad,
-                                                          _lib.ptr(bias), _lib.ptr(bias_begin), tb, no_ts, eos,
-                                                          max_initial, ts_state.data_ptr(), self._posr.data_ptr(),
-                                                          limit.data_ptr(), active.data_ptr(), log[c, 0].data_ptr(),
-                                                          log_lp[c, 1].data_ptr(), stream), "cbw_greedy_select")
+                    select((self._logits.data_ptr(), slots, self.vocab, self.vpad, _lib.ptr(bias), _lib.ptr(bias_begin),
+                            tb, no_ts, eos, max_initial, ts_state.data_ptr(), self._posr.data_ptr(), limit.data_ptr(),
+                            active.data_ptr(), log[c, 0].data_ptr(), log_lp[c, 1].data_ptr()), live, stream)
                     log[c, 2].copy_(active)
                     if c + 1 == left:
                         break
@@ -459,6 +471,8 @@ class DecoderEngine:
                         raise RuntimeError("GPU greedy bookkeeping diverged from the host replay")
                     seqs[slot] = seq
                     lps[slot] += new_lps
+                    if replayed is not None:
+                        replayed(live[slot], len(new_lps), finished)
                     if finished:
                         results[live[slot]] = (seq, lps[slot]) if return_logprobs else seq
                         live[slot], seqs[slot], lps[slot] = None, None, []
@@ -471,6 +485,55 @@ class DecoderEngine:
         ``return_logprobs`` (sequence, per-step log-probs)."""
         return self.greedy_windows([(enc_out, prefix)], eos, [max_length], bias, bias_begin, rules, check_every,
                                    return_logprobs)[0]
+
+    def sample_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], eos: int, max_lengths,
+                       bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules, temperature: float,
+                       generators, top_k: int = 50, check_every: int = 8, max_slots: int = 16) -> List:
+        """Temperature sampling (HF 4.37.2 sample branch of GenerationMixin.generate: the call of
+        pba_whisper.py:318-331 with do_sample = True, and every temperature > 0 rung of generate_with_fallback,
+        :425-442) for several windows in lock step with no host round trip per token: greedy_windows' driver with
+        cbw_sample_select as the step's choice (the processed scores of cbw_greedy_select, top-``top_k`` and
+        ``temperature`` warpers, the draw, the log-prob of the top-k-filtered scores).  The draw is torch.multinomial's
+        exponential race with its noise made here: per step and live window one ``exponential_`` of [V] numbers from
+        that window's own generator into the window's row of a noise buffer (an asynchronous torch op), so a
+        window's tokens depend neither on its slot nor on the other windows, and are the tokens sample_search draws
+        with an identically seeded generator (except where an fp32 tie in the race resolves differently).
+        ``generators``: one device torch.Generator per window (a single one for a single window), each used by no
+        other window.  Steps enqueued past a window's end consume draws; after the replay that ends a window its
+        generator is set back to the state right after the draw of its last token, where sample_search leaves it.
+        Returns (sequence incl. the prefix, per-step log-probs) per window, as sample_search."""
+        if not (temperature > 0 and math.isfinite(temperature)) or top_k < 1:
+            raise ValueError("sample_windows needs a finite temperature > 0 and top_k >= 1")
+        gens = [generators] if isinstance(generators, torch.Generator) else list(generators)
+        if len(gens) != len(windows) or len({id(g) for g in gens}) != len(gens):
+            raise ValueError("sample_windows needs one generator of its own per window")
+        V = self.vocab
+        noise: List[Optional[torch.Tensor]] = [None]
+        states: List[list] = [[] for _ in gens]   # per window: the generator's state after each draw since the last replay
+
+        def select(args, live, stream):
+            if noise[0] is None:
+                noise[0] = torch.ones((len(live), V), dtype=torch.float32, device=self.device)
+            for slot, w in enumerate(live):
+                if w is not None:
+                    noise[0][slot].exponential_(generator=gens[w])
+                    states[w].append(gens[w].get_state())
+            _lib.check(self.lib.cbw_sample_select(*args, float(temperature), int(top_k), noise[0].data_ptr(), V, stream),
+                       "cbw_sample_select")
+
+        def replayed(w, taken, finished):
+            if finished:
+                gens[w].set_state(states[w][taken - 1])
+            states[w].clear()
+        return self._lock_step("sample_windows", windows, eos, max_lengths, bias, bias_begin, rules, select,
+                               check_every, True, max_slots, replayed)
+
+    def sample_dev(self, enc_out: torch.Tensor, prefix: Sequence[int], eos: int, max_length: int,
+                   bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules, temperature: float,
+                   generator: torch.Generator, top_k: int = 50, check_every: int = 8):
+        """sample_windows over one window -> (sequence, per-step log-probs)."""
+        return self.sample_windows([(enc_out, prefix)], eos, [max_length], bias, bias_begin, rules, temperature,
+                                   [generator], top_k, check_every)[0]
 
     def sample_search(self, prefix: Sequence[int], eos: int, max_length: int, bias_at: callable, rules=None,
                       begin_index: int = 0, temperature: float = 0.0, top_k: int = 50,

@@ -294,6 +294,14 @@ hipError_t cbw_greedy_select_launch(const float* logits, int B, int V, int ld, c
                                     const float* bias_begin, int ts_begin, int no_ts, int eos, int max_initial,
                                     int* ts_state, const int* pos_rows, const int* limit, int* active, int* tokens,
                                     float* logprob, hipStream_t st);
+// cbw_greedy_select_launch's arguments, then the warpers and the race's noise f32 [B][noise_ld] (noise_ld >= V);
+// V <= CBW_SAMPLE_MAX_V: a block of 1024 threads holds its row's scores in 51 registers per thread
+constexpr int CBW_SAMPLE_MAX_V = 1024 * 51;
+hipError_t cbw_sample_select_launch(const float* logits, int B, int V, int ld, const float* bias,
+                                    const float* bias_begin, int ts_begin, int no_ts, int eos, int max_initial,
+                                    int* ts_state, const int* pos_rows, const int* limit, int* active, int* tokens,
+                                    float* logprob, float temperature, int top_k, const float* noise,
+                                    int64_t noise_ld, hipStream_t st);
 hipError_t cbw_logprob_topk_launch(const float* logits, int B, int V, int ld, const float* bias, int64_t bias_ld,
                                    int k, float* lp, int* idx, hipStream_t st);
 hipError_t cbw_timestamp_rules_launch(const float* logits, int B, int V, int ld, const float* bias, const int* state,

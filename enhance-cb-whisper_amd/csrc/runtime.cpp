@@ -3156,6 +3156,21 @@ int cbw_greedy_select(const float* logits, int B, int V, int ld, const float* bi
     return CBW_OK;
 }
 
+int cbw_sample_select(const float* logits, int B, int V, int ld, const float* bias, const float* bias_begin,
+                      int timestamp_begin, int no_timestamps, int eos, int max_initial, int32_t* ts_state,
+                      const int32_t* pos_rows, const int32_t* limit, int32_t* active, int32_t* tokens, float* logprob,
+                      float temperature, int top_k, const float* noise, int64_t noise_ld, cbw_stream_t stream) {
+    if (!logits || !ts_state || !pos_rows || !limit || !active || !tokens || !logprob || !noise || B < 1 || B > 16 ||
+        V < 1 || V > CBW_SAMPLE_MAX_V || ld < V || noise_ld < V)
+        return fail(CBW_ERR_INVALID, "bad arguments (B in [1, 16], V in [1, 52224], ld >= V, noise_ld >= V)");
+    if (!(temperature > 0.f) || !std::isfinite(temperature) || top_k < 1)
+        return fail(CBW_ERR_INVALID, "bad arguments (temperature > 0 and finite, top_k >= 1)");
+    HIPCHK(cbw_sample_select_launch(logits, B, V, ld, bias, bias_begin, timestamp_begin, no_timestamps, eos,
+                                    max_initial, ts_state, pos_rows, limit, active, tokens, logprob, temperature, top_k,
+                                    noise, noise_ld, (hipStream_t)stream));
+    return CBW_OK;
+}
+
 // ------------------------------------------------------------------ building block
 }  // extern "C"
 namespace {

@@ -6,6 +6,7 @@
 // src/model/cb_whisper.py:100-104, src/utils.py:188-192); see oracle/mel.py and
 // oracle/encoder.py for the restated algorithms these kernels are checked against.
 #include <algorithm>
+#include <cfloat>
 #include <cstdlib>
 #include <map>
 
@@ -1074,6 +1075,137 @@ __global__ __launch_bounds__(1024) void timestamp_rules_kernel(const float* __re
     }
 }
 
+// What greedy_select_kernel and sample_select_kernel share (1024-thread blocks, one row each).
+// SelectRow: the rule state of a row, derived from ts_state[r] = {n, last, second last, last timestamp} as the end of
+// beam_select_kernel derives it, and the mask of WhisperTimeStampLogitsProcessor without the mass rule
+// (ts_begin < 0: no timestamp rules, every token is text).
+struct SelectRow {
+    int sn, t1, tb, ts_floor, ts_begin, no_ts, eos, max_initial;
+    bool rules, last_ts, penult_ts, at_begin;
+    __device__ __forceinline__ SelectRow(const int* st, int V, int ts_begin_, int no_ts_, int eos_, int max_initial_)
+        : sn(st[0]), t1(st[1]), ts_begin(ts_begin_), no_ts(no_ts_), eos(eos_), max_initial(max_initial_) {
+        const int t2 = st[2], lts = st[3];
+        rules = ts_begin >= 0;
+        tb = rules ? ts_begin : V;   // text below, timestamps from tb on
+        last_ts = sn >= 1 && t1 >= tb;
+        penult_ts = sn < 2 || t2 >= tb;
+        at_begin = sn == 0;
+        ts_floor = lts < 0 ? tb : ((last_ts && !penult_ts) ? lts : lts + 1);
+    }
+    __device__ __forceinline__ bool masked(int i) const {
+        bool m = i == no_ts;
+        if (last_ts) m = m || (penult_ts ? i >= tb : i < eos);
+        m = m || (i >= tb && i < ts_floor);
+        if (at_begin) m = m || i < tb || (max_initial >= 0 && i > tb + max_initial);
+        return rules && m;
+    }
+};
+
+// f(i, score_i) for the thread's indices tid, tid + 1024, ... in ascending order; score = -inf where the row's mask
+// applies, else x[i] + bs[i] (bs may be NULL).  Unconditional loads of clamped indices, eight in flight, as
+// timestamp_rules_kernel.
+template <class F>
+__device__ __forceinline__ void select_for_each(const SelectRow& row, const float* __restrict__ x,
+                                                const float* __restrict__ bs, int V, F&& f) {
+    const float* bsrc = bs ? bs : x;
+    for (int i0 = threadIdx.x; i0 < V; i0 += 8 * 1024) {
+        float xv[8], bv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int ii = min(i0 + u * 1024, V - 1);
+            xv[u] = x[ii];
+            bv[u] = bsrc[ii];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * 1024;
+            if (i >= V) break;
+            f(i, row.masked(i) ? -INFINITY : xv[u] + (bs ? bv[u] : 0.f));
+        }
+    }
+}
+
+// (max, lowest index of it) over the block's 16 waves; nothing above -inf: index 0x7fffffff
+__device__ __forceinline__ void block_argmax16(float v, int i, float* red, int* redi, float& M, int& I) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const float wm = wave_max(v);
+    int ci = v == wm ? i : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ci = min(ci, __shfl_xor(ci, o, 64));
+    if (lane == 0) { red[wid] = wm; redi[wid] = ci; }
+    __syncthreads();
+    M = red[0];
+    I = redi[0];
+    for (int w = 1; w < 16; ++w)
+        if (red[w] > M || (red[w] == M && redi[w] < I)) { M = red[w]; I = redi[w]; }
+    __syncthreads();
+}
+__device__ __forceinline__ float block_sum16(float v, float* red) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    v = wave_sum(v);
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    float tot = 0.f;
+    for (int w = 0; w < 16; ++w) tot += red[w];
+    __syncthreads();
+    return tot;
+}
+
+// Two passes over a row's masked scores (each(f) calls f(i, score_i) over the thread's indices in ascending order;
+// tb = the row's first timestamp id), the same result in every thread: the max and its lowest index over the
+// text and over the timestamp tokens, their sums of exponentials, and the mass rule (logsumexp of the timestamp
+// scores > max text score: every text token is to be masked).
+struct SelectStats {
+    float m_text, m_ts, s_text, s_ts, lse_ts;
+    int i_text, i_ts;
+    bool force_ts;
+};
+template <class E>
+__device__ __forceinline__ SelectStats select_class_stats(int tb, E&& each, float* red, int* redi) {
+    SelectStats c;
+    float mt = -INFINITY, mts = -INFINITY;
+    int it = 0x7fffffff, its = 0x7fffffff;
+    each([&](int i, float v) {   // ascending indices: `>` keeps the lowest of a maximum; selects of values, so that
+                                 // the four stay in registers
+        const bool text = i < tb;
+        const bool ut = text && v > mt, us = !text && v > mts;
+        mt = ut ? v : mt;
+        it = ut ? i : it;
+        mts = us ? v : mts;
+        its = us ? i : its;
+    });
+    block_argmax16(mt, it, red, redi, c.m_text, c.i_text);
+    block_argmax16(mts, its, red, redi, c.m_ts, c.i_ts);
+    const float m_text = c.m_text, m_ts = c.m_ts;
+    float st = 0.f, sts = 0.f;
+    each([&](int i, float v) {
+        const bool text = i < tb;
+        const float e = text ? (m_text > -INFINITY ? __expf(v - m_text) : 0.f)
+                             : (m_ts > -INFINITY ? __expf(v - m_ts) : 0.f);
+        st += text ? e : 0.f;
+        sts += text ? 0.f : e;
+    });
+    c.s_text = block_sum16(st, red);
+    c.s_ts = block_sum16(sts, red);
+    c.lse_ts = m_ts > -INFINITY ? m_ts + logf(c.s_ts) : -INFINITY;
+    c.force_ts = c.lse_ts > m_text;
+    return c;
+}
+
+// The bookkeeping after row r's choice (one thread): ts_state advances by the token and
+// active[r] = token != eos && pos_rows[r] + 1 < limit[r].
+__device__ __forceinline__ void select_finish(const SelectRow& row, int r, int tok, float lp, int* ts_state,
+                                              const int* __restrict__ pos_rows, const int* __restrict__ limit,
+                                              int* active, int* __restrict__ tokens, float* __restrict__ logprob) {
+    ts_state[4 * r] = row.sn + 1;
+    ts_state[4 * r + 1] = tok;
+    ts_state[4 * r + 2] = row.t1;
+    if (row.rules && tok >= row.ts_begin) ts_state[4 * r + 3] = tok;
+    active[r] = (tok != row.eos && pos_rows[r] + 1 < limit[r]) ? 1 : 0;
+    tokens[r] = tok;
+    logprob[r] = lp;
+}
+
 // One greedy step's choice for every row of a lock-step decode, no host in the loop (HF 4.37.2 greedy search: the
 // processors on the raw logits, argmax, log_softmax of the processed scores for the fallback checks).  One block per
 // row, two passes over the row's V logits, eight loads in flight per thread in each:
@@ -1097,120 +1229,203 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
                                                              int* __restrict__ tokens, float* __restrict__ logprob) {
     __shared__ float red[16];
     __shared__ int redi[16];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (!active[r]) {   // the whole block: uniform, before any barrier
+        if (tid == 0) tokens[r] = eos;
+        return;
+    }
+    const float* x = logits + (int64_t)r * ld;
+    const SelectRow row(ts_state + 4 * r, V, ts_begin, no_ts, eos, max_initial);
+    const float* bs = row.sn == 0 ? bias_begin : bias;
+    const SelectStats c = select_class_stats(row.tb, [&](auto&& f) { select_for_each(row, x, bs, V, f); }, red, redi);
+    if (tid != 0) return;
+    const bool pick_ts = c.force_ts || c.m_ts > c.m_text;   // a tie across the boundary goes to the text token, the lower id
+    const float best = pick_ts ? c.m_ts : c.m_text;
+    int tok = pick_ts ? c.i_ts : c.i_text;
+    float lp = -INFINITY;
+    if (best > -INFINITY) {
+        const float M = fmaxf(c.m_text, c.m_ts);
+        const float lse = c.force_ts ? c.lse_ts
+                                     : M + logf((c.m_text > -INFINITY ? c.s_text * __expf(c.m_text - M) : 0.f) +
+                                                (c.m_ts > -INFINITY ? c.s_ts * __expf(c.m_ts - M) : 0.f));
+        lp = best - lse;
+    } else {
+        tok = eos;
+    }
+    select_finish(row, r, tok, lp, ts_state, pos_rows, limit, active, tokens, logprob);
+}
+
+// The order-preserving integer image of a float (a < b as floats <=> okey(a) < okey(b) as unsigned; -inf the lowest
+// of the ordered values) and its inverse: the radix select below works on it.
+__device__ __forceinline__ unsigned okey(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float okey_value(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// scores a thread of sample_select_kernel holds in registers: V <= 1024 * 51 = 52224 (Whisper's vocabularies: 51864 to
+// 51866)
+constexpr int SAMPLE_PER_THREAD = CBW_SAMPLE_MAX_V / 1024;
+
+// One sampling step's choice for every row of a lock-step decode, no host in the loop (HF 4.37.2 sample loop: the
+// processors on the raw logits, then TemperatureLogitsWarper and TopKLogitsWarper, torch.multinomial of the softmax,
+// log_softmax of the top-k-filtered processed scores for the fallback checks).  One block per row:
+//   s = the processed scores exactly as greedy_select_kernel forms them (SelectRow's masks, select_class_stats' two
+//   passes, then the mass rule's mask on the text tokens), read once into 51 registers per thread;
+//   kth = the top_k-th largest s, found exactly by a radix select on okey(s): four passes, each a 256-bin LDS
+//   histogram of one byte of the keys that match the bytes chosen so far (a thread adds a run of equal bins with one
+//   atomic: the high bytes of logits fall into a handful of bins), wave 0 scans the bins from the top;
+//   kept = {i : s_i > -inf and s_i >= kth} (ties at kth all kept; fewer than top_k finite: every finite one), tested
+//   on the keys;
+//   token = argmax over the kept i of (exp(s_i / T - max / T) / sum) / q_i in fp32, the form torch.multinomial's
+//   exponential race evaluates with q = noise[r][i] ~ Exp(1) (ties -> lower id; a q that is not positive and finite
+//   reads as FLT_MIN); logprob = s_token - logsumexp over the kept s.
+// Nothing finite left, or no kept index won (NaN scores): token eos, logprob -inf -- the token written is always in
+// [0, V) or eos.  The bookkeeping is greedy_select_kernel's (select_finish), so its position invariant holds here too.
+__global__ __launch_bounds__(1024) void sample_select_kernel(const float* __restrict__ logits, int V, int ld,
+                                                             const float* __restrict__ bias,
+                                                             const float* __restrict__ bias_begin, int ts_begin,
+                                                             int no_ts, int eos, int max_initial, int* ts_state,
+                                                             const int* __restrict__ pos_rows,
+                                                             const int* __restrict__ limit, int* active,
+                                                             int* __restrict__ tokens, float* __restrict__ logprob,
+                                                             float inv_t, int top_k, const float* __restrict__ noise,
+                                                             int64_t noise_ld) {
+    __shared__ float red[16];
+    __shared__ int redi[16];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sel[2];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     if (!active[r]) {   // the whole block: uniform, before any barrier
         if (tid == 0) tokens[r] = eos;
         return;
     }
     const float* x = logits + (int64_t)r * ld;
-    const int sn = ts_state[4 * r], t1 = ts_state[4 * r + 1], t2 = ts_state[4 * r + 2], lts = ts_state[4 * r + 3];
-    const float* bs = sn == 0 ? bias_begin : bias;
-    const bool rules = ts_begin >= 0;
-    const int tb = rules ? ts_begin : V;   // text below, timestamps from tb on; rules off: every token is text
-    const bool last_ts = sn >= 1 && t1 >= tb, penult_ts = sn < 2 || t2 >= tb, at_begin = sn == 0;
-    const int ts_floor = lts < 0 ? tb : ((last_ts && !penult_ts) ? lts : lts + 1);
-    auto masked = [&](int i) -> bool {
-        bool m = i == no_ts;
-        if (last_ts) m = m || (penult_ts ? i >= tb : i < eos);
-        m = m || (i >= tb && i < ts_floor);
-        if (at_begin) m = m || i < tb || (max_initial >= 0 && i > tb + max_initial);
-        return rules && m;
-    };
-    // (max, lowest index of it) over the block; nothing above -inf: index 0x7fffffff
-    auto block_argmax = [&](float v, int i, float& M, int& I) {
-        const float wm = wave_max(v);
-        int ci = v == wm ? i : 0x7fffffff;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ci = min(ci, __shfl_xor(ci, o, 64));
-        if (lane == 0) { red[wid] = wm; redi[wid] = ci; }
-        __syncthreads();
-        M = red[0];
-        I = redi[0];
-        for (int w = 1; w < 16; ++w)
-            if (red[w] > M || (red[w] == M && redi[w] < I)) { M = red[w]; I = redi[w]; }
-        __syncthreads();
-    };
-    auto block_sum = [&](float v) -> float {
-        v = wave_sum(v);
-        if (lane == 0) red[wid] = v;
-        __syncthreads();
-        float tot = 0.f;
-        for (int w = 0; w < 16; ++w) tot += red[w];
-        __syncthreads();
-        return tot;
-    };
-    // unconditional loads of clamped indices, as timestamp_rules_kernel; a thread walks its indices in ascending
-    // order, so `>` keeps the lowest index of its maximum
+    const float* q = noise + (int64_t)r * noise_ld;
+    const SelectRow row(ts_state + 4 * r, V, ts_begin, no_ts, eos, max_initial);
+    const float* bs = row.sn == 0 ? bias_begin : bias;
+    // the thread's scores, indices tid, tid + 1024, ...: loaded once, every later pass runs on registers (the masks
+    // applied here; beyond V: -inf, which no pass below counts as a score)
+    float s[SAMPLE_PER_THREAD];
     const float* bsrc = bs ? bs : x;
-    float mt = -INFINITY, mts = -INFINITY;
-    int it = 0x7fffffff, its = 0x7fffffff;
-    for (int i0 = tid; i0 < V; i0 += 8 * 1024) {
+#pragma unroll
+    for (int u0 = 0; u0 < SAMPLE_PER_THREAD; u0 += 8) {   // eight logits and biases in flight, as select_for_each
         float xv[8], bv[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int ii = min(i0 + u * 1024, V - 1);
-            xv[u] = x[ii];
-            bv[u] = bsrc[ii];
+        for (int u = u0; u < min(u0 + 8, SAMPLE_PER_THREAD); ++u) {
+            const int ii = min(tid + u * 1024, V - 1);
+            xv[u - u0] = x[ii];
+            bv[u - u0] = bsrc[ii];
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * 1024;
-            if (i >= V) break;
-            const float v = masked(i) ? -INFINITY : xv[u] + (bs ? bv[u] : 0.f);
-            if (i < tb) {
-                if (v > mt) { mt = v; it = i; }
-            } else if (v > mts) {
-                mts = v;
-                its = i;
+        for (int u = u0; u < min(u0 + 8, SAMPLE_PER_THREAD); ++u) {
+            const int i = tid + u * 1024;
+            // + 0.f: a score of -0.0 becomes +0.0 (equal as floats, one key)
+            s[u] = (i < V && !row.masked(i)) ? xv[u - u0] + (bs ? bv[u - u0] : 0.f) + 0.f : -INFINITY;
+        }
+        __builtin_amdgcn_sched_barrier(0);   // or all 102 loads are issued at once and the scores spill
+    }
+    // f(i, s_i) over the thread's indices in ascending order
+    auto scores = [&](auto&& f) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < SAMPLE_PER_THREAD; ++u) f(tid + u * 1024, s[u]);
+    };
+    const SelectStats c = select_class_stats(row.tb, scores, red, redi);
+    const float best = (c.force_ts || c.m_ts > c.m_text) ? c.m_ts : c.m_text;   // the maximum of the processed scores
+    if (!(best > -INFINITY)) {   // block-uniform: the stats are the same in every thread
+        if (tid == 0) select_finish(row, r, eos, -INFINITY, ts_state, pos_rows, limit, active, tokens, logprob);
+        return;
+    }
+    if (c.force_ts) {   // the mass rule: every text token masked
+#pragma unroll
+        for (int u = 0; u < SAMPLE_PER_THREAD; ++u)
+            if (tid + u * 1024 < row.tb) s[u] = -INFINITY;
+    }
+    // from here on the scores as their keys (okey_value gives a score back): the radix select's view, and no second
+    // set of 51 registers
+    unsigned key[SAMPLE_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < SAMPLE_PER_THREAD; ++u) key[u] = okey(s[u]);
+    auto keys = [&](auto&& f) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < SAMPLE_PER_THREAD; ++u) f(tid + u * 1024, key[u]);
+    };
+    unsigned prefix = 0, known = 0, remaining = (unsigned)min(top_k, V);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        unsigned run_bin = 0, run = 0;
+        keys([&](int, unsigned k) {
+            if ((k & known) != prefix) return;
+            const unsigned b = (k >> shift) & 255u;
+            if (run && b != run_bin) { atomicAdd(&hist[run_bin], run); run = 0; }
+            run_bin = b;
+            ++run;
+        });
+        if (run) atomicAdd(&hist[run_bin], run);
+        __syncthreads();
+        if (wid == 0) {   // lane l owns bins 255 - 4 l ... 252 - 4 l; the bin where the count from the top reaches `remaining`
+            unsigned cnt[4], tot = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cnt[j] = hist[255 - (4 * lane + j)]; tot += cnt[j]; }
+            unsigned inc = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            unsigned above = inc - tot;
+            if (above < remaining && remaining <= inc) {   // one lane: the keys that match number >= remaining
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (remaining <= above + cnt[j]) {
+                        sel[0] = 255u - (4 * lane + j);
+                        sel[1] = remaining - above;
+                        break;
+                    }
+                    above += cnt[j];
+                }
             }
         }
+        __syncthreads();
+        prefix |= sel[0] << shift;
+        known |= 255u << shift;
+        remaining = sel[1];
     }
-    float m_text, m_ts;
-    int i_text, i_ts;
-    block_argmax(mt, it, m_text, i_text);
-    block_argmax(mts, its, m_ts, i_ts);
-    float st = 0.f, sts = 0.f;
-    for (int i0 = tid; i0 < V; i0 += 8 * 1024) {
-        float xv[8], bv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int ii = min(i0 + u * 1024, V - 1);
-            xv[u] = x[ii];
-            bv[u] = bsrc[ii];
+    // prefix = okey(kth); kept: finite and >= kth (no score is -0.0, so the keys order equal scores equally)
+    const unsigned floor_key = max(prefix, okey(-INFINITY) + 1u);
+    const float max_w = best * inv_t;
+    float sw = 0.f, ss = 0.f;   // the kept set's sums: of the warped softmax, and of exp(s - max) for the log-prob
+    keys([&](int, unsigned k) {
+        if (k >= floor_key) {
+            const float v = okey_value(k);
+            sw += expf(v * inv_t - max_w);
+            ss += __expf(v - best);
         }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * 1024;
-            if (i >= V) break;
-            const float v = masked(i) ? -INFINITY : xv[u] + (bs ? bv[u] : 0.f);
-            if (i < tb) st += m_text > -INFINITY ? __expf(v - m_text) : 0.f;
-            else sts += m_ts > -INFINITY ? __expf(v - m_ts) : 0.f;
+    });
+    const float sum_w = block_sum16(sw, red), sum_s = block_sum16(ss, red);
+    float win = -1.f;   // p / q >= 0 for every kept index; a thread's indices ascend, so `>` keeps its lowest
+    int iw = 0x7fffffff;
+    keys([&](int i, unsigned k) {
+        if (k >= floor_key) {
+            float qi = q[i];
+            if (!(qi > 0.f && qi < INFINITY)) qi = FLT_MIN;
+            const float p = expf(okey_value(k) * inv_t - max_w) / sum_w / qi;
+            if (p > win) { win = p; iw = i; }
         }
-    }
-    const float s_text = block_sum(st), s_ts = block_sum(sts);
+    });
+    float pw;
+    int tok;
+    block_argmax16(win, iw, red, redi, pw, tok);
     if (tid != 0) return;
-    const float lse_ts = m_ts > -INFINITY ? m_ts + logf(s_ts) : -INFINITY;
-    const bool force_ts = lse_ts > m_text;
-    const bool pick_ts = force_ts || m_ts > m_text;   // a tie across the boundary goes to the text token, the lower id
-    const float best = pick_ts ? m_ts : m_text;
-    int tok = pick_ts ? i_ts : i_text;
     float lp = -INFINITY;
-    if (best > -INFINITY) {
-        const float M = fmaxf(m_text, m_ts);
-        const float lse = force_ts ? lse_ts
-                                   : M + logf((m_text > -INFINITY ? s_text * __expf(m_text - M) : 0.f) +
-                                              (m_ts > -INFINITY ? s_ts * __expf(m_ts - M) : 0.f));
-        lp = best - lse;
-    } else {
+    if (pw >= 0.f && tok >= 0 && tok < V)
+        lp = x[tok] + (bs ? bs[tok] : 0.f) - (best + logf(sum_s));
+    else
         tok = eos;
-    }
-    ts_state[4 * r] = sn + 1;
-    ts_state[4 * r + 1] = tok;
-    ts_state[4 * r + 2] = t1;
-    if (rules && tok >= ts_begin) ts_state[4 * r + 3] = tok;
-    active[r] = (tok != eos && pos_rows[r] + 1 < limit[r]) ? 1 : 0;
-    tokens[r] = tok;
-    logprob[r] = lp;
+    select_finish(row, r, tok, lp, ts_state, pos_rows, limit, active, tokens, logprob);
 }
 }  // namespace
 
@@ -1447,6 +1662,21 @@ hipError_t cbw_greedy_select_launch(const float* logits, int B, int V, int ld, c
     if (B < 1 || B > 16 || V < 1 || ld < V) return hipErrorInvalidValue;
     hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, logits, V, ld, bias, bias_begin, ts_begin,
                        no_ts, eos, max_initial, ts_state, pos_rows, limit, active, tokens, logprob);
+    return hipGetLastError();
+}
+
+hipError_t cbw_sample_select_launch(const float* logits, int B, int V, int ld, const float* bias,
+                                    const float* bias_begin, int ts_begin, int no_ts, int eos, int max_initial,
+                                    int* ts_state, const int* pos_rows, const int* limit, int* active, int* tokens,
+                                    float* logprob, float temperature, int top_k, const float* noise,
+                                    int64_t noise_ld, hipStream_t st) {
+    if (B < 1 || B > 16 || V < 1 || V > CBW_SAMPLE_MAX_V || ld < V || noise_ld < V || top_k < 1 || !(temperature > 0.f) ||
+        !(temperature < INFINITY))
+        return hipErrorInvalidValue;
+    // scores * (1 / T) in fp32, as torch divides a device tensor by a host scalar
+    hipLaunchKernelGGL(sample_select_kernel, dim3(B), dim3(1024), 0, st, logits, V, ld, bias, bias_begin, ts_begin,
+                       no_ts, eos, max_initial, ts_state, pos_rows, limit, active, tokens, logprob,
+                       1.0f / temperature, top_k, noise, noise_ld);
     return hipGetLastError();
 }
 

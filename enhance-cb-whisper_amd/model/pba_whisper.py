@@ -47,6 +47,12 @@ def _dev_greedy() -> bool:
     return os.environ.get("CBW_DEV_GREEDY", "1") != "0"
 
 
+def _dev_sample() -> bool:
+    """CBW_DEV_SAMPLE, read at call time: temperature sampling with the token choice on the GPU
+    (DecoderEngine.sample_dev) instead of the host loop of sample_search; 0 switches it off."""
+    return os.environ.get("CBW_DEV_SAMPLE", "1") != "0"
+
+
 def shortform_prefix(prompt: Sequence[int], init: Sequence[int], max_target_positions: int = 448) -> List[int]:
     """The forced decoder prefix of a short-form window with a keyword prompt, as transformers 4.37.2
     (requirements.txt:21) WhisperGenerationMixin._set_forced_decoder_ids builds it for pba_whisper.py:287-296: the
@@ -240,7 +246,12 @@ class PBAWhisper:
                       timestamps: bool = False, free: Optional[Dict] = None):
         """One window decoded token by token with the per-step log-probs of the fallback checks: temperature > 0
         samples (HF's sample loop: processors, then temperature + top-k 50 warpers, a seeded device RNG),
-        temperature 0 is greedy.  -> (sequence incl. the prefix, per-step log-probs)."""
+        temperature 0 is greedy.  -> (sequence incl. the prefix, per-step log-probs).
+        At temperature > 0 with a prefix of >= 2 tokens and no free language position the draw runs on the GPU
+        (DecoderEngine.sample_dev, cbw_sample_select: no host round trip per token; CBW_DEV_SAMPLE=0 switches it off).
+        For a seed it gives the tokens the host path (sample_search) draws, except where an fp32 tie in
+        torch.multinomial's race resolves differently, and it leaves ``generator`` in the state the host path leaves
+        it in."""
         n_forced = 1 + len(free["forced"]) if free else 0
         max_length = self._window_max_length(len(prefix) + n_forced, max_new_tokens)
         begin_pos = free["begin"] if free else len(prefix)
@@ -249,6 +260,10 @@ class PBAWhisper:
         if not (temperature and temperature > 0) and not free and len(prefix) >= 2 and _dev_greedy():
             return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin,
                                            self.rules if timestamps else None, return_logprobs=True)
+        if temperature and temperature > 0 and not free and len(prefix) >= 2 and generator is not None \
+                and _dev_sample():
+            return self.decoder.sample_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin,
+                                           self.rules if timestamps else None, temperature, generator)
         self.decoder.start(enc_out, 1)
         return self.decoder.sample_search(prefix, self.tokens.eot, max_length, bias_at,
                                           self.rules if timestamps else None, begin_pos, temperature or 0.0,

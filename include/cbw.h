@@ -452,6 +452,24 @@ int cbw_greedy_select(const float* logits, int B, int V, int ld, const float* bi
                       const int32_t* pos_rows, const int32_t* limit, int32_t* active, int32_t* tokens, float* logprob,
                       cbw_stream_t stream);
 
+/* One sampling step's choice for up to 16 rows on the GPU, so a temperature-sampling decode loop needs no host round
+ * trip per token (replaces the sample branch of GenerationMixin.generate, num_beams = 1 and do_sample = True, reached
+ * from pba_whisper.py:318-331 short-form and from every temperature > 0 rung of generate_with_fallback, :425-442).
+ * cbw_greedy_select's arguments and bookkeeping (ts_state, active, the position invariant, a row inactive on entry
+ * only gets tokens[r] = eos), with the choice replaced: s = the processed scores exactly as cbw_greedy_select forms
+ * them; the kept set is {i : s_i finite and s_i >= the top_k-th largest s} (TopKLogitsWarper: ties at the threshold
+ * all kept, exact; fewer than top_k finite scores: all of them); tokens[r] = argmax over the kept i of
+ * softmax_kept(s / temperature)_i / noise[r][i] in fp32 (ties -> lower id), which is torch.multinomial's draw when
+ * noise holds the Exp(1) numbers it would draw (noise f32 [B][noise_ld], noise_ld >= V; an entry that is not positive
+ * and finite reads as FLT_MIN); logprob[r] = s[token] - logsumexp over the kept s (log_softmax of the top-k-filtered
+ * scores at temperature 1, what HF's fallback checks read); nothing finite left: eos and -inf.  tokens[r] is always in
+ * [0, V) or eos.  Does not allocate or synchronise and draws no random numbers itself.  B in [1, 16], V in [1, 52224]
+ * (a workgroup holds its row's scores in registers), ld >= V, temperature > 0 and finite, top_k >= 1. */
+int cbw_sample_select(const float* logits, int B, int V, int ld, const float* bias, const float* bias_begin,
+                      int timestamp_begin, int no_timestamps, int eos, int max_initial, int32_t* ts_state,
+                      const int32_t* pos_rows, const int32_t* limit, int32_t* active, int32_t* tokens, float* logprob,
+                      float temperature, int top_k, const float* noise, int64_t noise_ld, cbw_stream_t stream);
+
 /* ---------------------------------------------------------------- building blocks (tests, tools)
  * NHWC bf16 implicit-GEMM convolution, y = act(conv(x, w) + bias (+ res)).
  * x [N][H][W][Cin], w [Cout][KH][KW][Cin], res/y [N][Ho][Wo][Cout]; Cin % 64 == 0, Cout % 64 == 0.
