@@ -102,6 +102,9 @@ SIGNATURES = {
                                      c_int, c_int, c_void_p, c_void_p]),
     "cbw_kws_sim_resize_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                        c_int, c_int, c_void_p, c_void_p]),
+    "cbw_resample_len": (c_int64, [c_int64, c_int, c_int]),
+    "cbw_resample_ws_bytes": (c_int64, [c_int, c_int]),
+    "cbw_resample": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "cbw_mel": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "cbw_mel_long": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cbw_encoder_create": (c_int, [ctypes.POINTER(EncoderConfig), ctypes.POINTER(c_void_p)]),

@@ -40,11 +40,14 @@ def hs_frames(n_samples: int) -> int:
     return int(math.ceil((n // HOP) / 2.0))
 
 
-def extract_hidden_states(pcm, encoder, layer_ids: Sequence[int] = tuple(range(10, 22))) -> torch.Tensor:
-    """utils.py:182-195 on the GPU: 16 kHz mono pcm -> f32 [len(layer_ids), t_len, D], per-frame
-    L2-normalised (cbw_mel + cbw_encoder_hs)."""
-    from .whisper import log_mel
+def extract_hidden_states(pcm, encoder, layer_ids: Sequence[int] = tuple(range(10, 22)),
+                          sample_rate: int = 16000) -> torch.Tensor:
+    """utils.py:179-195 on the GPU: pcm [len] or [C, len] at ``sample_rate`` -> channel mean, resampled to
+    16 kHz (cbw_resample; 16 kHz mono passes through untouched) -> f32 [len(layer_ids), t_len, D], per-frame
+    L2-normalised (cbw_mel + cbw_encoder_hs); t_len counts the frames of the resampled audio."""
+    from .whisper import log_mel, resample
     pcm = torch.as_tensor(np.asarray(pcm, dtype=np.float32)).to(encoder.device)
+    pcm = resample(pcm, sample_rate)
     _, pk = log_mel(pcm, encoder.n_mel, packed=True)
     hs = encoder.hidden_states(pk, list(layer_ids), normalize=True)[0]
     return hs[:, : hs_frames(pcm.numel())].contiguous()
@@ -187,9 +190,20 @@ class KeywordDatabase:
 
 
 def build_split_folder(split_folder: str, keywords: Sequence[str], audios: Dict[int, np.ndarray], encoder,
-                       kw_type: str = "tts", layer_ids: Sequence[int] = tuple(range(10, 22))) -> None:
+                       kw_type: str = "tts", layer_ids: Sequence[int] = tuple(range(10, 22)),
+                       sample_rates=None) -> None:
     """Write the layout efficient_kws/dataset.py reads: text/keywords.txt and
-    keywords-hs/<kw_type>/<idx>.bin for every keyword index that has audio (others stay ghosts)."""
+    keywords-hs/<kw_type>/<idx>.bin for every keyword index that has audio (others stay ghosts).
+    ``sample_rates``: None (every audio is 16 kHz), one rate for all, or a dict with the rate of every
+    keyword index in ``audios`` (an index it lacks raises: a guessed rate would go unnoticed); each audio
+    is [len] or [C, len] and is downmixed and resampled by ``extract_hidden_states``."""
+    if isinstance(sample_rates, dict):
+        missing = sorted(set(audios) - set(sample_rates))
+        if missing:
+            raise ValueError(f"sample_rates has no rate for keyword indices {missing}")
+        rates = {i: sample_rates[i] for i in audios}
+    else:
+        rates = {i: 16000 if sample_rates is None else sample_rates for i in audios}
     os.makedirs(os.path.join(split_folder, "text"), exist_ok=True)
     out = os.path.join(split_folder, "keywords-hs", kw_type)
     os.makedirs(out, exist_ok=True)
@@ -197,4 +211,5 @@ def build_split_folder(split_folder: str, keywords: Sequence[str], audios: Dict[
         f.write("\n".join(keywords) + "\n")
     width = len(str(len(keywords) - 1))
     for i, pcm in audios.items():
-        write_bin(os.path.join(out, str(i).zfill(width) + ".bin"), extract_hidden_states(pcm, encoder, layer_ids))
+        write_bin(os.path.join(out, str(i).zfill(width) + ".bin"),
+                  extract_hidden_states(pcm, encoder, layer_ids, sample_rate=rates[i]))

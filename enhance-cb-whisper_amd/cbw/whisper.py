@@ -23,6 +23,63 @@ def cpad_for(n_mel: int) -> int:
     return (n_mel + 63) // 64 * 64
 
 
+SAMPLE_RATE = 16000
+_resample_ws = _lib.Workspace()
+
+
+def load_wav(path: str) -> Tuple[torch.Tensor, int]:
+    """A PCM WAV file through the standard library's ``wave`` module -> (f32 [C, len] on the host in [-1, 1),
+    sample_rate): 8-bit unsigned, 16-bit and 32-bit signed integer samples, scaled by 2^-(bits - 1).  Every other
+    container or encoding (float WAV, 24-bit, FLAC, MP3, ...) stays the caller's job: decode it to samples and pass
+    them with their rate to ``resample`` / ``extract_hidden_states``."""
+    import wave
+    with wave.open(path, "rb") as w:
+        channels, width, rate, frames = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        raw = w.readframes(frames)
+    if width == 1:
+        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    elif width == 2:
+        x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    elif width == 4:
+        x = (np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
+    else:
+        raise ValueError(f"{path}: {8 * width}-bit samples are not read here (8, 16 or 32-bit integer PCM)")
+    return torch.from_numpy(np.ascontiguousarray(x.reshape(-1, channels).T)), rate
+
+
+def resample(pcm, sample_rate: int, target: int = SAMPLE_RATE, device: Optional[torch.device] = None) -> torch.Tensor:
+    """``torchaudio.functional.resample(torch.mean(waveform, dim=0), sample_rate, target)`` on the GPU (cbw_resample;
+    src/utils.py:179-184, src/efficient_kws/dataset.py:472-483): pcm [len] or [C, len] (tensor or array, host or
+    device) -> f32 device tensor [ceil(len * target / sample_rate)].  Mono audio already at ``target`` is passed
+    through untouched (moved to the device as f32 if it is not there yet)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if int(sample_rate) != sample_rate or int(target) != target:
+        raise ValueError(f"sample rates must be integers, got {sample_rate} -> {target}")
+    sample_rate, target = int(sample_rate), int(target)
+    if sample_rate < 1 or target < 1:
+        raise ValueError(f"sample rates must be >= 1, got {sample_rate} -> {target}")
+    x = pcm if torch.is_tensor(pcm) else torch.as_tensor(np.asarray(pcm, dtype=np.float32))
+    if x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[0] < 1):
+        raise ValueError(f"expected pcm [len] or [C, len], got {tuple(x.shape)}")
+    if device is None:
+        device = x.device if x.is_cuda else torch.device(f"cuda:{torch.cuda.current_device()}")
+    x = x.to(device=device, dtype=torch.float32).contiguous()
+    channels, n = (1, x.shape[0]) if x.dim() == 1 else (x.shape[0], x.shape[1])
+    if sample_rate == target and channels == 1:
+        return x.reshape(-1)
+    out_len = lib.cbw_resample_len(n, sample_rate, target)
+    nb = lib.cbw_resample_ws_bytes(sample_rate, target)
+    if out_len < 0 or nb < 0:
+        _lib.check(-1, "cbw_resample")
+    out = torch.empty(out_len, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = _resample_ws.get(nb, x.device)
+        _lib.check(lib.cbw_resample(x.data_ptr(), channels, n, sample_rate, target, out.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), _lib.stream_handle()), "cbw_resample")
+    return out
+
+
 def log_mel(pcm: torch.Tensor, n_mel: int, packed: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """pcm f32 [n] (device) -> (mel f32 [n_mel, 3000], time-major bf16 [3000, cpad] or None)."""
     _lib.require_gpu()

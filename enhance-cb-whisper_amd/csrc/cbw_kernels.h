@@ -250,6 +250,14 @@ hipError_t cbw_mel_frames(const float* pcm, int n_samples, const float* filters,
                           float* logmel, int n_mel, hipStream_t st, int L_pad = 0, int frames = 0);
 hipError_t cbw_mel_finish(float* logmel, int n_mel, float* scratch, uint16_t* packed, int cpad, hipStream_t st,
                           int frames = 0);
+// polyphase resampler with the downmix in its loads: pcm f32 [C][len] -> out f32 [out_len],
+// out[f n + j] = sum_k mean_c(xpad)[f o + k] * tab[k n + j] (tab phase-minor: [T][n], T = 2 width + o; xpad = x behind
+// `width` zeros, zero past its end too).  The table is staged in LDS where n * T <= CBW_RESAMPLE_LDS_FLOATS.
+constexpr int CBW_RESAMPLE_LDS_FLOATS = 8192;   // 32 KB of the 160 KB LDS: several blocks still share a CU
+hipError_t cbw_resample_taps(const float* pcm, int C, int64_t len, const float* tab, int o, int n, int width, int T,
+                             float* out, int64_t out_len, hipStream_t st);
+// out[i] = mean over the C rows of pcm [C][len]
+hipError_t cbw_downmix(const float* pcm, int C, int64_t len, float* out, hipStream_t st);
 hipError_t cbw_layernorm(const float* x, const float* g, const float* b, uint16_t* y, float* y32, int rows, int D,
                          float eps, hipStream_t st);
 hipError_t cbw_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int H, int hd, hipStream_t st);

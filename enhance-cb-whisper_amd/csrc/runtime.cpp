@@ -11,6 +11,8 @@
 #include <limits>
 #include <map>
 #include <memory>
+#include <mutex>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -2343,6 +2345,115 @@ int cbw_kws_band_scaled(const float* logits, const float* ghost, int K, float th
         return CBW_OK;
     }
     HIPCHK(cbw_spot(logits, ghost, K, thr, coef, 3, nullptr, idx, n, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+// ------------------------------------------------------------------ resample + downmix
+namespace {
+struct ResamplePlan {
+    int o = 1, n = 1, width = 0, T = 0;   // reduced rates, half width, taps per phase (T = 0: orig == new)
+    int64_t entries = 0;                  // n * T
+};
+
+// torchaudio _get_sinc_resample_kernel's sizes (lowpass_filter_width 6, rolloff 0.99), in its float64 arithmetic
+int resample_plan(int orig, int new_, ResamplePlan* p) {
+    if (orig < 1 || new_ < 1) return fail(CBW_ERR_INVALID, "resample: sample rates must be >= 1");
+    const int g = std::gcd(orig, new_);
+    p->o = orig / g;
+    p->n = new_ / g;
+    if (p->o == p->n) return CBW_OK;
+    const double base = std::min(p->o, p->n) * 0.99;
+    const double width = std::ceil(6.0 * p->o / base);
+    const double entries = (2.0 * width + p->o) * p->n;
+    if (entries > (double)CBW_RESAMPLE_MAX_TABLE)
+        return fail(CBW_ERR_INVALID, "resample: " + std::to_string(orig) + " -> " + std::to_string(new_) + " needs " +
+                                         std::to_string(p->n) + " phases x " + std::to_string((int64_t)(2.0 * width + p->o)) +
+                                         " taps, above CBW_RESAMPLE_MAX_TABLE entries");
+    p->width = (int)width;
+    p->T = 2 * p->width + p->o;
+    p->entries = (int64_t)p->n * p->T;
+    return CBW_OK;
+}
+
+// kernel[j][k] in float64, rounded to fp32 once, stored phase-minor: tab[k * n + j]
+void resample_table(const ResamplePlan& p, float* tab) {
+    const double base = std::min(p.o, p.n) * 0.99, scale = base / p.o;
+    for (int k = 0; k < p.T; ++k)
+        for (int j = 0; j < p.n; ++j) {
+            double t = (-(double)j / p.n + (double)(k - p.width) / p.o) * base;
+            t = std::min(6.0, std::max(-6.0, t));
+            const double c = std::cos(t * M_PI / 12.0), a = t * M_PI;
+            tab[(size_t)k * p.n + j] = (float)((a == 0.0 ? 1.0 : std::sin(a) / a) * c * c * scale);
+        }
+}
+
+// a rate pair's table in pinned host memory, built on first use and kept for the process (the source of the
+// stream-ordered upload must outlive the call)
+int resample_host_table(const ResamplePlan& p, const float** out) {
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, float*> tables;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = tables.find({p.o, p.n});
+    if (it == tables.end()) {
+        void* host = nullptr;
+        if (hipHostMalloc(&host, (size_t)p.entries * sizeof(float), hipHostMallocPortable) != hipSuccess)
+            return fail(CBW_ERR_OOM, "resample: hipHostMalloc of the coefficient table failed");
+        resample_table(p, (float*)host);
+        it = tables.emplace(std::make_pair(p.o, p.n), (float*)host).first;
+    }
+    *out = it->second;
+    return CBW_OK;
+}
+
+int resample_len(int64_t n, const ResamplePlan& p, int64_t* out) {
+    if (n < 0) return fail(CBW_ERR_INVALID, "resample: n < 0");
+    if (n > (std::numeric_limits<int64_t>::max() - p.o) / p.n) return fail(CBW_ERR_INVALID, "resample: n * new_ overflows");
+    *out = (n * p.n + p.o - 1) / p.o;
+    return CBW_OK;
+}
+}  // namespace
+
+int64_t cbw_resample_len(int64_t n, int orig, int new_) {
+    ResamplePlan p;
+    int64_t len = 0;
+    if (n < 0) return fail(CBW_ERR_INVALID, "resample: n < 0");
+    CHK(resample_plan(orig, new_, &p));
+    CHK(resample_len(n, p, &len));
+    return len;
+}
+
+int64_t cbw_resample_ws_bytes(int orig, int new_) {
+    ResamplePlan p;
+    CHK(resample_plan(orig, new_, &p));
+    return p.entries * (int64_t)sizeof(float);
+}
+
+int cbw_resample(const float* pcm, int channels, int64_t n, int orig, int new_, float* out, void* ws, int64_t ws_bytes,
+                 cbw_stream_t stream) {
+    if (!pcm || !out) return fail(CBW_ERR_INVALID, "cbw_resample: null pcm or out");
+    if (channels < 1) return fail(CBW_ERR_INVALID, "cbw_resample: channels < 1");
+    if (n < 0) return fail(CBW_ERR_INVALID, "cbw_resample: n < 0");
+    ResamplePlan p;
+    int64_t out_len = 0;
+    CHK(resample_plan(orig, new_, &p));
+    CHK(resample_len(n, p, &out_len));
+    if (n > std::numeric_limits<int64_t>::max() / channels)
+        return fail(CBW_ERR_INVALID, "cbw_resample: channels * n overflows");
+    if ((std::max(out_len, n) + 255) / 256 > 0x7fffffffLL)
+        return fail(CBW_ERR_INVALID, "cbw_resample: more than 2^31 - 1 blocks of 256 samples");
+    if (p.T && (!ws || ((uintptr_t)ws & 3) || ws_bytes < p.entries * (int64_t)sizeof(float)))
+        return fail(CBW_ERR_INVALID, "cbw_resample: ws null, misaligned or smaller than cbw_resample_ws_bytes");
+    if (n == 0) return CBW_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!p.T) {
+        if (channels == 1) HIPCHK(hipMemcpyAsync(out, pcm, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        else HIPCHK(cbw_downmix(pcm, channels, n, out, st));
+        return CBW_OK;
+    }
+    const float* host = nullptr;
+    CHK(resample_host_table(p, &host));
+    HIPCHK(hipMemcpyAsync(ws, host, (size_t)p.entries * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(cbw_resample_taps(pcm, channels, n, (const float*)ws, p.o, p.n, p.width, p.T, out, out_len, st));
     return CBW_OK;
 }
 

@@ -97,6 +97,54 @@ __global__ void mel_finish_kernel(float* __restrict__ logmel, int n_mel, const f
     }
 }
 
+// ---------------------------------------------------------------- resample + downmix (in front of the log-mel)
+// torchaudio.functional.resample(torch.mean(waveform, dim=0), orig, new) with the sinc_interp_hann defaults, as the
+// reference calls it (src/utils.py:179-184, src/efficient_kws/dataset.py:472-483): a polyphase filter of n phases x T
+// taps (o = orig / gcd, n = new / gcd, T = 2 width + o), y[f n + j] = sum_k xpad[f o + k] kernel[j][k] with xpad = x
+// behind `width` zeros.  The coefficient table is the runtime's (float64 on the host, rounded once).
+//
+// sample i of the downmixed input: the mean over the C rows of pcm [C][len] (the channel sum in channel order, one
+// division), 0 outside [0, len).  The index is clamped so that the load stays inside the buffer and the value is
+// selected afterwards: no padded copy of the input exists.
+__device__ __forceinline__ float downmix_at(const float* __restrict__ pcm, int C, int64_t len, int64_t i) {
+    const int64_t ic = i < 0 ? 0 : (i >= len ? len - 1 : i);
+    float s = pcm[ic];
+    for (int c = 1; c < C; ++c) s += pcm[(int64_t)c * len + ic];
+    if (C > 1) s /= (float)C;
+    return (i >= 0 && i < len) ? s : 0.f;
+}
+
+// one thread per output sample; tab is phase-minor, tab[k * n + j] = kernel[j][k], so that the 256 consecutive
+// outputs of a block (consecutive phases) read consecutive coefficients: coalesced from global memory, one bank each
+// from LDS.  LDS: the whole table staged per block (the launcher picks it where n * T floats fit).  One fmaf per tap,
+// k ascending from 0, in either variant: an output's bits depend on neither the variant nor the launch shape.
+template <bool LDS>
+__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ pcm, int C, int64_t len,
+                                                       const float* __restrict__ tab, int o, int n, int width, int T,
+                                                       float* __restrict__ out, int64_t out_len) {
+    extern __shared__ float coef[];
+    if (LDS) {
+        for (int i = threadIdx.x; i < n * T; i += blockDim.x) coef[i] = tab[i];
+        __syncthreads();
+    }
+    const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (m >= out_len) return;
+    const int64_t f = m / n;
+    const int j = (int)(m - f * n);
+    const int64_t i0 = f * o - width;
+    const float* __restrict__ cf = (LDS ? coef : tab) + j;
+    float acc = 0.f;
+    for (int k = 0; k < T; ++k) acc = fmaf(downmix_at(pcm, C, len, i0 + k), cf[(int64_t)k * n], acc);
+    out[m] = acc;
+}
+
+// orig == new with C > 1: the downmix alone
+__global__ __launch_bounds__(256) void downmix_kernel(const float* __restrict__ pcm, int C, int64_t len,
+                                                      float* __restrict__ out) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < len) out[i] = downmix_at(pcm, C, len, i);
+}
+
 // ---------------------------------------------------------------- LayerNorm (one wave per row)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, bf16* __restrict__ y,
@@ -1696,6 +1744,26 @@ hipError_t cbw_mel_finish(float* logmel, int n_mel, float* scratch, uint16_t* pa
     hipLaunchKernelGGL(max_reduce_kernel, dim3(parts), dim3(1024), 0, st, logmel, (int64_t)n_mel * frames, scratch);
     hipLaunchKernelGGL(mel_finish_kernel, dim3(1024), dim3(256), 0, st, logmel, n_mel, scratch, parts, (bf16*)packed,
                        cpad, frames);
+    return hipGetLastError();
+}
+
+hipError_t cbw_resample_taps(const float* pcm, int C, int64_t len, const float* tab, int o, int n, int width, int T,
+                             float* out, int64_t out_len, hipStream_t st) {
+    const int64_t blocks = (out_len + 255) / 256;
+    if (C < 1 || len < 1 || out_len < 1 || blocks > 0x7fffffffLL || T != 2 * width + o) return hipErrorInvalidValue;
+    if ((int64_t)n * T <= CBW_RESAMPLE_LDS_FLOATS)
+        hipLaunchKernelGGL(resample_kernel<true>, dim3((unsigned)blocks), dim3(256), (size_t)n * T * sizeof(float), st,
+                           pcm, C, len, tab, o, n, width, T, out, out_len);
+    else
+        hipLaunchKernelGGL(resample_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pcm, C, len, tab, o, n,
+                           width, T, out, out_len);
+    return hipGetLastError();
+}
+
+hipError_t cbw_downmix(const float* pcm, int C, int64_t len, float* out, hipStream_t st) {
+    const int64_t blocks = (len + 255) / 256;
+    if (C < 1 || len < 1 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(downmix_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pcm, C, len, out);
     return hipGetLastError();
 }
 

@@ -308,6 +308,34 @@ int cbw_kws_band(const float* logits, const float* ghost, int K, float thr, floa
 int cbw_kws_band_scaled(const float* logits, const float* ghost, int K, float thr, float coef, int32_t* idx,
                         int32_t* n, cbw_stream_t stream);
 
+/* ---------------------------------------------------------------- resample + downmix
+ * Replaces `torch.mean(waveform, dim=0)` + `torchaudio.functional.resample(waveform, sample_rate, 16000)` in front
+ * of the feature extractor (utils.py:179-184, efficient_kws/dataset.py:472-483): torchaudio's sinc_interp_hann
+ * defaults (lowpass_filter_width 6, rolloff 0.99) as a polyphase filter.  With g = gcd(orig, new_), o = orig / g,
+ * n = new_ / g:  base = min(o, n) * 0.99, width = ceil(6 o / base), T = 2 width + o taps in each of n phases,
+ *   t[j][k] = clamp((-j / n + (k - width) / o) * base, -6, 6),
+ *   kernel[j][k] = sinc(pi t) * cos^2(pi t / 12) * base / o        (sinc(0) = 1),
+ *   y[f n + j] = sum_k xpad[f o + k] * kernel[j][k],  xpad = x with `width` zeros in front and width + o behind,
+ * y cut to cbw_resample_len = ceil(n * len / o) samples.  The table is evaluated in float64 on the host and rounded
+ * to fp32 once (torchaudio evaluates it in fp32: bit parity with torchaudio is not the aim); the sum
+ * is fp32 fmaf in ascending k, so a sample's bits do not depend on the launch shape or on where the input lies.
+ * pcm f32 [channels][n] (device); each tap reads the mean over the channels (their sum in channel order, divided
+ * once: the mean first, then the filter, the reference's order); out f32 [cbw_resample_len(n, orig, new_)].
+ * orig == new_: a copy (channels == 1) or the mean alone; cbw_resample_ws_bytes is then 0 and ws is not read.
+ * ws (4-byte aligned, >= cbw_resample_ws_bytes(orig, new_) = n T floats) receives the table by a stream-ordered copy.
+ * The first call of a process for a rate pair evaluates that pair's table into pinned host memory, which is kept;
+ * every later call neither allocates nor synchronises.
+ * CBW_ERR_INVALID (checked in this order, nothing launched): pcm or out null; channels < 1; n < 0; a rate < 1;
+ * a table of more than CBW_RESAMPLE_MAX_TABLE = 2^20 entries (4 MiB: 44100 -> 16000 needs 160 x 475 = 76 000,
+ * 16001 -> 16000 would need 16000 x 16015 and is refused); n * new_ / o or its launch grid out of range
+ * (more than 2^31 - 1 blocks of 256 outputs); ws null, misaligned or smaller than cbw_resample_ws_bytes.
+ * The two helpers return CBW_ERR_INVALID (-1) for the arguments cbw_resample refuses.  n == 0 returns CBW_OK.   */
+#define CBW_RESAMPLE_MAX_TABLE (1 << 20)
+int64_t cbw_resample_len(int64_t n, int orig, int new_);
+int64_t cbw_resample_ws_bytes(int orig, int new_);
+int cbw_resample(const float* pcm, int channels, int64_t n, int orig, int new_, float* out, void* ws,
+                 int64_t ws_bytes, cbw_stream_t stream);
+
 /* ---------------------------------------------------------------- Whisper front end
  * Replaces WhisperFeatureExtractor(padding='max_length') (utils.py:186-187).
  * pcm f32 [n] (16 kHz) -> out f32 [n_mel][3000]; packed (optional) bf16 [3000][cpad]
