@@ -144,6 +144,11 @@ SIGNATURES = {
     "cbw_decoder_cross_attn_probs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                              c_int64, c_void_p, c_void_p]),
     "cbw_dtw": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cbw_token_ts_ws_bytes": (c_int64, [c_int, c_int]),
+    "cbw_align_matrix": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_void_p]),
+    "cbw_dtw_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                            c_void_p]),
     "cbw_logprob_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cbw_timestamp_rules": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p]),

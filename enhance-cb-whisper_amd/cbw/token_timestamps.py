@@ -8,6 +8,8 @@ matrix gives a monotone path, and each text position's first frame on the path, 
 The weights come from libcbw (cbw_decoder_cross_attn_probs: a teacher-forced decoder pass over the row, one query row
 per position -- what generate's per-step cross_attentions hold for the row that was kept, the beam's history being the
 row's prefix); the DTW runs on the host in libcbw (cbw_dtw, the transformers loop step for step).
+``extract_token_timestamps_dev`` is the same extraction with the matrix and the DTW on the GPU (cbw_align_matrix,
+cbw_dtw_dev); ``extract_token_timestamps`` stays the reference it is tested against and its fallback.
 
 ``variant``:
   * "4.37" (the pinned transformers, requirements.txt:21): every decoder position is a DTW row; timestamps has the
@@ -83,6 +85,63 @@ def extract_token_timestamps(weights: torch.Tensor, median_filter_width: int = 7
         return ts
     n0 = num_input_ids or 0
     return torch.cat([torch.zeros(n0), torch.tensor(jump_times), torch.tensor([jump_times[-1]])]).float()
+
+
+_dev_ws = _lib.Workspace()
+
+
+def extract_token_timestamps_dev(weights: torch.Tensor, median_filter_width: int = 7, time_precision: float = 0.02,
+                                 num_frames: Optional[int] = None, variant: str = "4.37",
+                                 num_input_ids: Optional[int] = None) -> torch.Tensor:
+    """``extract_token_timestamps`` with the alignment matrix and the DTW on the GPU (cbw_align_matrix, cbw_dtw_dev on
+    the current stream; one copy back of the jump frames and the degenerate flag): the same arguments, the same
+    float32 tensor.  The host function itself answers where fewer than 2 positions are left, where the width is even
+    or above 7 (its own error for an even one), and where a frame's variance over the positions is zero or not finite
+    (the host path's NaNs are not restated).  weights [heads, positions, 1500], as cbw_decoder_cross_attn_probs writes
+    them (fewer frames are padded to that row pitch first); at most 1024 positions."""
+    if variant not in ("4.37", "5.x"):
+        raise ValueError(f"unknown variant {variant}")
+    host = lambda: extract_token_timestamps(weights, median_filter_width, time_precision, num_frames, variant,  # noqa: E731
+                                            num_input_ids)
+    width = int(median_filter_width)
+    if width <= 0 or width % 2 != 1 or width > 7:
+        return host()
+    if weights.dim() != 3 or weights.shape[0] < 1 or not 1 <= weights.shape[-1] <= 1500:
+        raise ValueError(f"expected weights [heads, positions, frames <= 1500], got {tuple(weights.shape)}")
+    n, T_all, frames = weights.shape
+    t0 = int(num_input_ids) if variant == "5.x" and num_input_ids is not None else 0
+    T = T_all - t0
+    F = frames if num_frames is None else min(frames, int(num_frames) // 2)
+    if T < 2:
+        return host()
+    _lib.require_gpu()
+    lib = _lib.load()
+    nb = lib.cbw_token_ts_ws_bytes(T, F)
+    if nb < 0:
+        _lib.check(-1, "cbw_token_ts_ws_bytes")
+    dev = weights.device if weights.is_cuda else torch.device(f"cuda:{torch.cuda.current_device()}")
+    w = weights.to(device=dev, dtype=torch.float32)
+    if frames < 1500:   # the kernels read rows of 1500 frames, cbw_decoder_cross_attn_probs' pitch
+        w = torch.nn.functional.pad(w, (0, 1500 - frames))
+    w = w.contiguous()
+    matrix = torch.empty((T, F), dtype=torch.float32, device=dev)
+    out = torch.empty(T + 1, dtype=torch.int32, device=dev)   # first_frame [T], then the flag
+    with torch.cuda.device(dev):
+        ws = _dev_ws.get(nb, dev)
+        st = _lib.stream_handle()
+        _lib.check(lib.cbw_align_matrix(w.data_ptr(), n, T_all, t0, T, F, width, matrix.data_ptr(),
+                                        out.data_ptr() + 4 * T, ws.data_ptr(), ws.numel(), st), "cbw_align_matrix")
+        _lib.check(lib.cbw_dtw_dev(matrix.data_ptr(), T, F, out.data_ptr(), None, None, None, ws.data_ptr(),
+                                   ws.numel(), st), "cbw_dtw_dev")
+    got = out.cpu().numpy()
+    if got[T]:
+        return host()
+    jump_times = got[:T].astype(np.int64) * time_precision
+    if variant == "4.37":
+        ts = torch.zeros(T_all + 1, dtype=torch.float32)
+        ts[1:] = torch.tensor(jump_times)
+        return ts
+    return torch.cat([torch.zeros(t0), torch.tensor(jump_times), torch.tensor([jump_times[-1]])]).float()
 
 
 def alignment_pairs(alignment_heads: Sequence[Sequence[int]]) -> np.ndarray:

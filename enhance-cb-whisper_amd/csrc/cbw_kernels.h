@@ -279,6 +279,17 @@ hipError_t cbw_dec_attention(const uint16_t* q, int ldq, const uint16_t* kc, con
 // keys (row pitch D): out f32 [T][n_keys] (token-level timestamps)
 hipError_t cbw_dec_cross_probs(const uint16_t* q, int ldq, const uint16_t* kc, int n_keys, int T, int D, int head,
                                float* out, hipStream_t st);
+// token-level timestamps behind the probabilities.  align_matrix: probs f32 [n][T_all][1500] (cbw_dec_cross_probs'
+// layout), positions [t0, t0 + T), the first F frames, odd width <= 7 -> matrix f32 [T][F], the negated head mean of
+// the median-filtered normalised weights; *degenerate (zeroed by the caller) |= 1 on a zero / non-finite variance.
+// dtw: matrix f32 [T][F], T <= 1024 -> first_frame int32 [T] and, where text_idx is given, the path as cbw_dtw writes
+// it; trace: cbw_dtw_trace_words(T, F) words of scratch.
+constexpr int CBW_DTW_MAX_F = 1500;   // the encoder frames of a window
+int64_t cbw_dtw_trace_words(int T, int F);
+hipError_t cbw_align_matrix_launch(const float* probs, int n, int T_all, int t0, int T, int F, int width,
+                                   float* matrix, int* degenerate, hipStream_t st);
+hipError_t cbw_dtw_launch(const float* matrix, int T, int F, int* first_frame, int* text_idx, int* time_idx, int* len,
+                          uint32_t* trace, hipStream_t st);
 hipError_t cbw_dec_reorder_kv(uint16_t* ks, uint16_t* vs, const int* rows, int B, int n_layers, int64_t layer_elems,
                               int64_t row_elems, int64_t copy_elems, hipStream_t st);
 // decode-step self-attention in one launch: row r (its own K/V batch r) over min(n_keys, n_keys_pos[nk_rows ? r : 0]

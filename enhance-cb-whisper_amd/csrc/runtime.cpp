@@ -3199,6 +3199,48 @@ int cbw_dtw(const double* matrix, int rows, int cols, int32_t* text_idx, int32_t
     return CBW_OK;
 }
 
+// The device statement of what follows the weights in _extract_token_timestamps: no allocation, no synchronisation.
+int64_t cbw_token_ts_ws_bytes(int T, int F) {
+    if (T < 1 || T > 1024 || F < 1 || F > CBW_DTW_MAX_F)
+        return fail(CBW_ERR_INVALID, "cbw_token_ts_ws_bytes needs 1 <= T <= 1024, 1 <= F <= 1500");
+    return cbw_dtw_trace_words(T, F) * (int64_t)sizeof(uint32_t);
+}
+
+namespace {
+static int token_ts_ws_check(const char* who, int T, int F, const void* ws, int64_t ws_bytes) {
+    if (!ws || ((uintptr_t)ws & 3) || ws_bytes < cbw_dtw_trace_words(T, F) * (int64_t)sizeof(uint32_t))
+        return fail(CBW_ERR_INVALID, std::string(who) + ": ws null, misaligned or smaller than cbw_token_ts_ws_bytes");
+    return CBW_OK;
+}
+}  // namespace
+
+int cbw_align_matrix(const float* probs, int n, int T_all, int t0, int T, int F, int width, float* matrix,
+                     int32_t* degenerate, void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    if (!probs || !matrix || !degenerate) return fail(CBW_ERR_INVALID, "cbw_align_matrix: null probs, matrix or degenerate");
+    if (n < 1) return fail(CBW_ERR_INVALID, "cbw_align_matrix: n < 1");
+    if (T < 2 || T > 1024) return fail(CBW_ERR_INVALID, "cbw_align_matrix needs 2 <= T <= 1024");
+    if (t0 < 0 || T_all < T || t0 > T_all - T) return fail(CBW_ERR_INVALID, "cbw_align_matrix: [t0, t0 + T) outside [0, T_all)");
+    if (F < 1 || F > 1500) return fail(CBW_ERR_INVALID, "cbw_align_matrix needs 1 <= F <= 1500");
+    if (width < 1 || width > 7 || !(width & 1)) return fail(CBW_ERR_INVALID, "cbw_align_matrix: width must be 1, 3, 5 or 7");
+    CHK(token_ts_ws_check("cbw_align_matrix", T, F, ws, ws_bytes));
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(degenerate, 0, sizeof(int32_t), st));
+    HIPCHK(cbw_align_matrix_launch(probs, n, T_all, t0, T, F, width, matrix, degenerate, st));
+    return CBW_OK;
+}
+
+int cbw_dtw_dev(const float* matrix, int T, int F, int32_t* first_frame, int32_t* text_idx, int32_t* time_idx,
+                int32_t* len, void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    if (!matrix || !first_frame) return fail(CBW_ERR_INVALID, "cbw_dtw_dev: null matrix or first_frame");
+    if (!!text_idx != !!time_idx || !!text_idx != !!len)
+        return fail(CBW_ERR_INVALID, "cbw_dtw_dev: text_idx, time_idx and len are all null or all set");
+    if (T < 1 || T > 1024) return fail(CBW_ERR_INVALID, "cbw_dtw_dev needs 1 <= T <= 1024");
+    if (F < 1 || F > CBW_DTW_MAX_F) return fail(CBW_ERR_INVALID, "cbw_dtw_dev needs 1 <= F <= 1500");
+    CHK(token_ts_ws_check("cbw_dtw_dev", T, F, ws, ws_bytes));
+    HIPCHK(cbw_dtw_launch(matrix, T, F, first_frame, text_idx, time_idx, len, (uint32_t*)ws, (hipStream_t)stream));
+    return CBW_OK;
+}
+
 int cbw_decoder_reorder(cbw_decoder* h, const int32_t* src_rows, int B, int Benc, int len, void* state,
                         int64_t state_bytes, cbw_stream_t stream) {
     if (!h || !src_rows || !state) return fail(CBW_ERR_INVALID, "null argument");

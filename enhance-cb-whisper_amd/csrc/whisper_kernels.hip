@@ -465,6 +465,194 @@ __global__ __launch_bounds__(256) void dec_cross_probs_kernel(const bf16* __rest
     for (int j = tid; j < n_keys; j += 256) out[(int64_t)r * n_keys + j] = ps[j] * inv;
 }
 
+// ---------------------------------------------------------------- token-level timestamps behind the probabilities
+// transformers' _extract_token_timestamps after the weights (pba_whisper.py:333-336, 425-442; the host statement is
+// cbw/token_timestamps.py): the alignment matrix and its dynamic time warping.
+//
+// Alignment matrix: matrix[t][f] = -(1/n) sum_h median_k z_h[t][reflect(f + k - W/2)], z_h[t][f] = (w - mean) / std
+// over the T positions [t0, t0 + T) of head h at frame f (population std).  One block per tile of 32 - 2 (W / 2) frames;
+// thread = (row group g of 32, column lane of 32): lane l holds frame reflect(f0 - W/2 + l), so that a half wave owns
+// a tile with its halo and the W neighbours of a median come by lane shuffles.  Per head: the mean in float64 (32
+// partial sums over the rows g, g + 32, ..., added in g order), the variance in float64 in a second pass, z with one
+// rounding to fp32, the median by exact selection, and the head sum in fp32 kept in the output itself: element (t, f)
+// is read and written by the same thread for h = 0, 1, ..., n - 1, the last one dividing by n and negating.
+// *degenerate |= 1 where a variance of a used frame is zero or not finite (the host path gives NaN there).
+constexpr int AM_G = 32;   // row groups of a block (1024 threads)
+
+template <int W>
+__device__ __forceinline__ float median_of(float (&v)[W]) {
+    // bubble network, unrolled: after pass p the p + 1 largest stand at the end; W / 2 + 1 passes fix v[W / 2]
+#pragma unroll
+    for (int p = 0; p <= W / 2; ++p)
+#pragma unroll
+        for (int q = 0; q + 1 < W - p; ++q) {
+            const float lo = fminf(v[q], v[q + 1]), hi = fmaxf(v[q], v[q + 1]);
+            v[q] = lo;
+            v[q + 1] = hi;
+        }
+    return v[W / 2];
+}
+
+template <int W>
+__global__ __launch_bounds__(32 * AM_G) void align_matrix_kernel(const float* __restrict__ probs, int n, int T_all,
+                                                                 int t0, int T, int F, float* __restrict__ matrix,
+                                                                 int* __restrict__ degenerate) {
+    constexpr int P = W / 2, FT = 32 - 2 * P;
+    __shared__ double part[AM_G][33];
+    const int lane = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int c = blockIdx.x * FT - P + lane;   // the lane's column before the reflection
+    int fr = c < 0 ? -c : c;
+    if (fr >= F) fr = 2 * (F - 1) - fr;
+    fr = min(max(fr, 0), F - 1);                // lanes behind the last halo: some frame, never stored
+    const bool inner = lane >= P && lane < 32 - P && c < F;
+    for (int h = 0; h < n; ++h) {
+        const float* __restrict__ w = probs + ((int64_t)h * T_all + t0) * 1500 + fr;
+        double s = 0.0;
+        for (int t = g; t < T; t += AM_G) s += (double)w[(int64_t)t * 1500];
+        part[g][lane] = s;
+        __syncthreads();
+        double mean = 0.0;
+        for (int q = 0; q < AM_G; ++q) mean += part[q][lane];
+        mean /= (double)T;
+        __syncthreads();
+        s = 0.0;
+        for (int t = g; t < T; t += AM_G) {
+            const double d = (double)w[(int64_t)t * 1500] - mean;
+            s += d * d;
+        }
+        part[g][lane] = s;
+        __syncthreads();
+        double var = 0.0;
+        for (int q = 0; q < AM_G; ++q) var += part[q][lane];
+        var /= (double)T;
+        __syncthreads();
+        if (g == 0 && !(var > 0.0 && var <= DBL_MAX)) atomicOr(degenerate, 1);
+        const double sd = sqrt(var);
+        for (int tb = 0; tb < T; tb += AM_G) {   // uniform trip count: every lane takes part in the shuffles
+            const int t = tb + g, tc = min(t, T - 1);
+            const float z = (float)(((double)w[(int64_t)tc * 1500] - mean) / sd);
+            float v[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k) v[k] = W == 1 ? z : __shfl(z, (lane + k - P) & 31, 32);
+            const float med = median_of<W>(v);
+            if (inner && t < T) {
+                float* o = matrix + (int64_t)t * F + c;
+                float acc = h ? *o + med : med;
+                if (h == n - 1) acc = -(acc / (float)n);
+                *o = acc;
+            }
+        }
+    }
+}
+
+// Dynamic time warping of matrix f32 [T][F] with cbw_dtw's arithmetic (fp32 tables, +inf borders around cost 0,
+// strict comparisons: the diagonal, then the row above, else the column to the left; cost = min + matrix as one fp32
+// add): an anti-diagonal wavefront.  One workgroup, thread i = text row i; at step d it computes cell (i, d - i) from
+// its own previous cost (a register), the cost thread i - 1 posted at step d - 1 (LDS, double-buffered: one barrier per
+// step) and the one it read from there a step earlier.  The steps go in blocks of 16: a thread loads the 16 matrix
+// entries of the next block (contiguous in its row) while it works on the current one, and packs the 16 trace entries
+// (2 bits each) of a block into one word, trace[block][i].  Then thread 0 walks the trace back from (T, F), holding
+// the current word in a register, and writes first_frame[i] = the time index at which the path enters row i and, if
+// asked, the path (backwards; the block reverses it in place afterwards).
+constexpr int DTW_MAX_T = 1024;
+__device__ __forceinline__ void dtw_lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// the 16 entries m[i][jb .. jb + 15] of a block of steps: one clamped load each and no branch, so that the loads of
+// the next block stay counted in flight behind those of the current one (entries outside [0, F) are never used)
+__device__ __forceinline__ void dtw_load16(const float* __restrict__ mr, int jb, int F, float (&buf)[16]) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) buf[k] = mr[min(max(jb + k, 0), F - 1)];
+}
+
+// the 16 steps of block b for text row i: returns the packed trace word
+__device__ __forceinline__ uint32_t dtw_block16(const float (&mv)[16], int b, int i, bool row, int F,
+                                                float (&sh)[2][DTW_MAX_T], float& left, float& diag) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {   // step d = 16 b + k: d & 1 == k & 1
+        const int j = 16 * b + k - i;
+        if (row && j >= 0 && j < F) {
+            const float up = i ? sh[(k & 1) ^ 1][i - 1] : INFINITY;
+            float c;
+            uint32_t t;
+            if (diag < up && diag < left) c = diag, t = 0;
+            else if (up < diag && up < left) c = up, t = 1;
+            else c = left, t = 2;
+            c += mv[k];
+            sh[k & 1][i] = c;
+            left = c;
+            diag = up;
+            word |= t << (2 * k);
+        }
+        dtw_lds_barrier();
+    }
+    return word;
+}
+
+__global__ __launch_bounds__(DTW_MAX_T) void dtw_kernel(const float* __restrict__ m, int T, int F,
+                                                        int* __restrict__ first_frame, int* __restrict__ text_idx,
+                                                        int* __restrict__ time_idx, int* __restrict__ len,
+                                                        uint32_t* __restrict__ trace) {
+    __shared__ float sh[2][DTW_MAX_T];
+    __shared__ int n_sh;
+    const int i = threadIdx.x;
+    const bool row = i < T;
+    const float* __restrict__ mr = m + (int64_t)min(i, T - 1) * F;
+    const int nblk = (T + F - 1 + 15) >> 4;
+    float ma[16], mb[16];   // two blocks of matrix entries, used in turn: no copy between them
+    dtw_load16(mr, -i, F, ma);
+    float left = INFINITY, diag = i == 0 ? 0.f : INFINITY;
+    for (int b = 0; b < nblk; b += 2) {
+        dtw_load16(mr, 16 * (b + 1) - i, F, mb);
+        const uint32_t wa = dtw_block16(ma, b, i, row, F, sh, left, diag);
+        if (row) trace[(int64_t)b * T + i] = wa;
+        if (b + 1 == nblk) break;
+        dtw_load16(mr, 16 * (b + 2) - i, F, ma);
+        const uint32_t wb = dtw_block16(mb, b + 1, i, row, F, sh, left, diag);
+        if (row) trace[(int64_t)(b + 1) * T + i] = wb;
+    }
+    __syncthreads();   // the trace words of every wave are in memory
+    if (i == 0) {
+        int r = T, c = F, n = 0;   // 1-based, as cbw_dtw's tables: row 0 walks left, column 0 walks up
+        int64_t at = -1;
+        uint32_t word = 0;
+        while (r > 0 || c > 0) {
+            if (text_idx) {
+                text_idx[n] = r - 1;
+                time_idx[n] = c - 1;
+            }
+            ++n;
+            uint32_t t;
+            if (c == 0) t = 1;
+            else if (r == 0) t = 2;
+            else {
+                const int d = r + c - 2;
+                const int64_t idx = (int64_t)(d >> 4) * T + (r - 1);
+                if (idx != at) word = trace[idx], at = idx;
+                t = (word >> (2 * (d & 15))) & 3u;
+            }
+            if (t != 2) first_frame[r - 1] = c - 1, --r;
+            if (t != 1) --c;
+        }
+        n_sh = n;
+        if (len) *len = n;
+    }
+    __syncthreads();
+    if (text_idx) {
+        const int n = n_sh;
+        for (int k = i; k < n / 2; k += blockDim.x) {
+            const int a = text_idx[k], b = text_idx[n - 1 - k];
+            text_idx[k] = b, text_idx[n - 1 - k] = a;
+            const int p = time_idx[k], q = time_idx[n - 1 - k];
+            time_idx[k] = q, time_idx[n - 1 - k] = p;
+        }
+    }
+}
+
 // Split-key decode attention (flash-decoding): workgroup = (key chunk of DS_CHUNK keys, head, kv batch)
 // serving ALL the R query rows that share the kv batch (the beams of a window against its cross K/V: K/V
 // read once, not once per beam).  With one chunk the workgroup writes the output; otherwise each writes
@@ -1521,6 +1709,33 @@ hipError_t cbw_dec_cross_probs(const uint16_t* q, int ldq, const uint16_t* kc, i
     if (n_keys > DA_MAXK || n_keys <= 0 || T <= 0 || head < 0 || (head + 1) * 64 > D) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dec_cross_probs_kernel, dim3(T), dim3(256), 0, st, (const bf16*)q, ldq, (const bf16*)kc, n_keys,
                        D, head, out);
+    return hipGetLastError();
+}
+
+int64_t cbw_dtw_trace_words(int T, int F) { return (int64_t)T * ((T + F - 1 + 15) >> 4); }
+
+hipError_t cbw_align_matrix_launch(const float* probs, int n, int T_all, int t0, int T, int F, int width,
+                                   float* matrix, int* degenerate, hipStream_t st) {
+    if (n < 1 || T < 1 || t0 < 0 || t0 + T > T_all || F < 1 || F > 1500 || width < 1 || width > 7 || !(width & 1))
+        return hipErrorInvalidValue;
+    if (F <= width / 2) width = 1;   // median_filter leaves such a short row as it is
+    const int tile = 32 - 2 * (width / 2);
+    const dim3 grid((F + tile - 1) / tile), block(32 * AM_G);
+    switch (width) {
+    case 1: hipLaunchKernelGGL(align_matrix_kernel<1>, grid, block, 0, st, probs, n, T_all, t0, T, F, matrix, degenerate); break;
+    case 3: hipLaunchKernelGGL(align_matrix_kernel<3>, grid, block, 0, st, probs, n, T_all, t0, T, F, matrix, degenerate); break;
+    case 5: hipLaunchKernelGGL(align_matrix_kernel<5>, grid, block, 0, st, probs, n, T_all, t0, T, F, matrix, degenerate); break;
+    default: hipLaunchKernelGGL(align_matrix_kernel<7>, grid, block, 0, st, probs, n, T_all, t0, T, F, matrix, degenerate);
+    }
+    return hipGetLastError();
+}
+
+hipError_t cbw_dtw_launch(const float* matrix, int T, int F, int* first_frame, int* text_idx, int* time_idx, int* len,
+                          uint32_t* trace, hipStream_t st) {
+    if (T < 1 || T > DTW_MAX_T || F < 1 || F > CBW_DTW_MAX_F) return hipErrorInvalidValue;
+    // the x dimension of the grid stays free for a batch of matrices
+    hipLaunchKernelGGL(dtw_kernel, dim3(1), dim3((T + 63) / 64 * 64), 0, st, matrix, T, F, first_frame, text_idx,
+                       time_idx, len, trace);
     return hipGetLastError();
 }
 

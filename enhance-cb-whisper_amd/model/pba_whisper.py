@@ -53,6 +53,12 @@ def _dev_sample() -> bool:
     return os.environ.get("CBW_DEV_SAMPLE", "1") != "0"
 
 
+def _dev_token_ts() -> bool:
+    """CBW_DEV_TOKEN_TS, read at call time: the alignment matrix and the DTW of token-level timestamps on the GPU
+    (cbw.token_timestamps.extract_token_timestamps_dev) instead of torch ops and the host DTW; 0 switches it off."""
+    return os.environ.get("CBW_DEV_TOKEN_TS", "1") != "0"
+
+
 def shortform_prefix(prompt: Sequence[int], init: Sequence[int], max_target_positions: int = 448) -> List[int]:
     """The forced decoder prefix of a short-form window with a keyword prompt, as transformers 4.37.2
     (requirements.txt:21) WhisperGenerationMixin._set_forced_decoder_ids builds it for pba_whisper.py:287-296: the
@@ -594,8 +600,9 @@ class PBAWhisper:
     def token_timestamps(self, segment: torch.Tensor, row: Sequence[int], num_frames: Optional[int] = None,
                          variant: str = "4.37", num_input_ids: Optional[int] = None) -> torch.Tensor:
         """Token-level timestamps of a decoded row (decoder input ids included) of the 30 s window ``segment``
-        [1, n_mel, 3000]: float32 [len(row)] (cbw.token_timestamps.extract_token_timestamps)."""
-        from cbw.token_timestamps import alignment_pairs, extract_token_timestamps
+        [1, n_mel, 3000]: float32 [len(row)] (cbw.token_timestamps.extract_token_timestamps_dev; with
+        CBW_DEV_TOKEN_TS=0 extract_token_timestamps, the host statement of the same)."""
+        from cbw.token_timestamps import alignment_pairs, extract_token_timestamps, extract_token_timestamps_dev
         if not self.alignment_heads:
             raise ValueError("token-level timestamps need the checkpoint's alignment_heads")
         row = [int(t) for t in row]
@@ -604,7 +611,8 @@ class PBAWhisper:
         enc = self.encode(self._pack(segment))
         self.decoder.start(enc, 1)
         w = self.decoder.cross_attn_probs(row[:-1], alignment_pairs(self.alignment_heads))
-        return extract_token_timestamps(w, self.median_filter_width, 0.02, num_frames, variant, num_input_ids)
+        extract = extract_token_timestamps_dev if _dev_token_ts() else extract_token_timestamps
+        return extract(w, self.median_filter_width, 0.02, num_frames, variant, num_input_ids)
 
     @staticmethod
     def _segment_out(s_):

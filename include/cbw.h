@@ -431,6 +431,32 @@ int cbw_decoder_cross_attn_probs(cbw_decoder* h, const int32_t* tokens, int T, c
  * [rows][cols] (host, row-major; the negated, normalised, median-filtered mean alignment weights); writes the
  * warping path as text_idx / time_idx (host int32, >= rows + cols entries) and its length to *len. */
 int cbw_dtw(const double* matrix, int rows, int cols, int32_t* text_idx, int32_t* time_idx, int* len);
+/* Token-level timestamps on the GPU: what transformers' _extract_token_timestamps (reached from pba_whisper.py:333-336,
+ * 425-442) does with the weights, beside the host statement in cbw/token_timestamps.py, which stays the reference and
+ * the fallback.  Every pointer is device memory; nothing allocates or synchronises.
+ * cbw_align_matrix: probs f32 [n][T_all][1500] (cbw_decoder_cross_attn_probs' output), the positions [t0, t0 + T)
+ *   (t0 > 0: the "5.x" variant, which drops the decoder input ids before normalising), the first F frames and an odd
+ *   median width in {1, 3, 5, 7} -> matrix f32 [T][F], row-major: the negated head mean of the median-filtered
+ *   normalised weights.  Per head and frame the mean over the T positions and the population variance (second pass,
+ *   sum (w - mean)^2 / T) in float64, z = (float)((w - mean) / sqrt(var)), the median along the frames by exact
+ *   selection with torch's reflect padding (none where F <= width / 2), the heads summed in fp32 in ascending order,
+ *   divided by n, negated.  *degenerate (int32) is 0, or non-zero where a variance among the used frames is zero or
+ *   not finite: the host path gives NaN there and the matrix is then not to be used.
+ * cbw_dtw_dev: matrix f32 [T][F] -> first_frame int32 [T], the time index at which the warping path enters each text
+ *   row (the jump frames of _extract_token_timestamps), by cbw_dtw's arithmetic bit for bit (fp32 tables, strict
+ *   comparisons: diagonal, row above, else left).  text_idx / time_idx (int32, >= T + F entries) and len (int32) are
+ *   all NULL, or all set and receive what cbw_dtw writes for the same matrix.  One workgroup, one thread per text row.
+ * ws (4-byte aligned, >= cbw_token_ts_ws_bytes(T, F) = 4 T ceil((T + F - 1) / 16) bytes) holds the DTW's trace, 2 bits
+ *   per cell in words of 16 anti-diagonals per text row; cbw_align_matrix keeps its statistics on chip and only checks
+ *   ws, so that one buffer serves both calls.
+ * CBW_ERR_INVALID before any GPU work for: a null pointer; n < 1; T < 2 (matrix) or T < 1 (DTW); T > 1024; t0 < 0 or
+ *   t0 + T > T_all; F < 1 or F > 1500; an even width or one above 7; path pointers partly set; ws null, misaligned or
+ *   too small.  cbw_token_ts_ws_bytes returns CBW_ERR_INVALID (-1) for a T or F that the two refuse.              */
+int64_t cbw_token_ts_ws_bytes(int T, int F);
+int cbw_align_matrix(const float* probs, int n, int T_all, int t0, int T, int F, int width, float* matrix,
+                     int32_t* degenerate, void* ws, int64_t ws_bytes, cbw_stream_t stream);
+int cbw_dtw_dev(const float* matrix, int T, int F, int32_t* first_frame, int32_t* text_idx, int32_t* time_idx,
+                int32_t* len, void* ws, int64_t ws_bytes, cbw_stream_t stream);
 int cbw_decoder_reorder(cbw_decoder* h, const int32_t* src_rows, int B, int Benc, int len, void* state,
                         int64_t state_bytes, cbw_stream_t stream);
 /* HF beam-search scores: log_softmax(logits) + bias, and their top-k (k <= 16, ties -> lower id) per
