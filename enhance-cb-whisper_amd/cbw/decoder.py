@@ -165,15 +165,28 @@ class DecoderEngine:
                                                     self._state.data_ptr(), self._state.numel(),
                                                     _lib.stream_handle()), "cbw_decoder_reorder")
 
+    def _timestamp_rules(self, logits_ptr: int, rows: int, bias: Optional[torch.Tensor], st: torch.Tensor, rules,
+                         out: torch.Tensor, stream: int):
+        """The one cbw_timestamp_rules call: ``rows`` rows of logits at ``logits_ptr`` with rule states ``st``
+        (int32 [rows, 4]) -> out f32 [rows, V] = the shared ``bias`` + the rows' timestamp masks."""
+        _lib.check(self.lib.cbw_timestamp_rules(logits_ptr, rows, self.vocab, self.vpad, _lib.ptr(bias), st.data_ptr(),
+                                                rules.timestamp_begin, rules.no_timestamps, rules.eos,
+                                                rules.max_initial, out.data_ptr(), stream), "cbw_timestamp_rules")
+
+    def _logprob_topk(self, logits_ptr: int, rows: int, bias: Optional[torch.Tensor], bias_ld: int, k: int,
+                      lp: torch.Tensor, idx: torch.Tensor, stream: int):
+        """The one cbw_logprob_topk call: top ``k`` of log_softmax(logits) + bias per row (bias [V] shared with
+        bias_ld 0, or [rows, bias_ld]) -> lp f32 / idx int32 [rows, k]."""
+        _lib.check(self.lib.cbw_logprob_topk(logits_ptr, rows, self.vocab, self.vpad, _lib.ptr(bias), bias_ld, k,
+                                             lp.data_ptr(), idx.data_ptr(), stream), "cbw_logprob_topk")
+
     def topk(self, k: int, bias: Optional[torch.Tensor] = None, bias_ld: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """HF beam-search scores log_softmax(logits) + bias (bias [V] shared, or [rows, bias_ld])."""
         rows = self._shape[0]
         lp = torch.empty((rows, k), dtype=torch.float32, device=self.device)
         idx = torch.empty((rows, k), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cbw_logprob_topk(self._logits.data_ptr(), rows, self.vocab, self.vpad,
-                                                 _lib.ptr(bias), bias_ld, k, lp.data_ptr(), idx.data_ptr(),
-                                                 _lib.stream_handle()), "cbw_logprob_topk")
+            self._logprob_topk(self._logits.data_ptr(), rows, bias, bias_ld, k, lp, idx, _lib.stream_handle())
         return lp.cpu().numpy(), idx.cpu().numpy()
 
     def timestamp_bias(self, rules, sampled_rows, bias: Optional[torch.Tensor], states=None) -> torch.Tensor:
@@ -185,127 +198,56 @@ class DecoderEngine:
         st = torch.tensor(states, dtype=torch.int32).to(self.device)
         out = torch.empty((rows, self.vocab), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cbw_timestamp_rules(self._logits.data_ptr(), rows, self.vocab, self.vpad,
-                                                    _lib.ptr(bias), st.data_ptr(), rules.timestamp_begin,
-                                                    rules.no_timestamps, rules.eos, rules.max_initial,
-                                                    out.data_ptr(), _lib.stream_handle()), "cbw_timestamp_rules")
+            self._timestamp_rules(self._logits.data_ptr(), rows, bias, st, rules, out, _lib.stream_handle())
         return out
 
     def beam_search_dev(self, prefix: Sequence[int], num_beams: int, eos: int, max_length: int, k: int,
                         bias_at: callable, rules=None, begin_index: int = 0, decoder_prompt_len: int = 1,
                         length_penalty: float = 1.0, check_every: int = 8, return_score: bool = False):
-        """cbw.generate.beam_search with the bookkeeping on the GPU: per token the
-        scores (timestamp rules from a device-side state, cbw_timestamp_rules; log-softmax + top-k), the
-        next-beam choice (cbw_beam_select), the KV reorder by the device parent rows and the decode step are
-        enqueued without a host round trip; every ``check_every`` tokens the logged candidates are copied back
-        once and replayed through the same BeamProcess the host search runs, which finds the end (EOS
-        hypotheses, early stop, max_length) and the result.  Steps enqueued past the end are discarded.
+        """cbw.generate.beam_search with the bookkeeping on the GPU, for the one window of the
+        last start(): one _BeamWindow at slot 0.  Per token its score() (timestamp rules from a device-side state,
+        log-softmax + top-k, the next-beam choice of cbw_beam_select), the KV reorder by the device parent rows and
+        the decode step, both reading the step's log row in place, are enqueued without a host round trip; every
+        ``check_every`` tokens its replay() copies the logged candidates back once and runs them through the same
+        BeamProcess the host search runs, which finds the end (EOS hypotheses, early stop, max_length) and the
+        result.  Steps enqueued past the end are discarded.
         Returns None when the engine cannot run it (Benc != 1, k or rows > 16): use beam_search."""
-        from .generate import BeamProcess
         rows, Benc = self._shape
         if Benc != 1 or rows != num_beams or rows > 16 or k > 16 or k != 2 * num_beams or len(prefix) < 2:
             return None
-        dev = self.device
-        bp = BeamProcess(prefix, num_beams, eos, max_length, length_penalty, decoder_prompt_len)
-        n_max = max(1, max_length - len(prefix))
-        lp = torch.empty((rows, k), dtype=torch.float32, device=dev)
-        idx = torch.empty((rows, k), dtype=torch.int32, device=dev)
-        scores = torch.tensor([0.0] + [-1e9] * (rows - 1), dtype=torch.float64, device=dev)
-        # one log row per step, every field a column range of one byte buffer, so a replay is ONE device -> host
-        # copy (six separate .cpu() calls cost ~33 copy launches per replay)
-        f_cs, f_cr, f_ct = 0, 8 * k, 12 * k
-        f_nt, f_nr, f_ok = 16 * k, 16 * k + 4 * rows, 16 * k + 8 * rows
-        row_bytes = (f_ok + 4 + 7) // 8 * 8
-        log_buf = torch.zeros((n_max, row_bytes), dtype=torch.uint8, device=dev)
-
-        def fields(buf):
-            return (buf[:, f_cs:f_cr].view(torch.float64), buf[:, f_cr:f_ct].view(torch.int32),
-                    buf[:, f_ct:f_nt].view(torch.int32), buf[:, f_nt:f_nr].view(torch.int32),
-                    buf[:, f_nr:f_ok].view(torch.int32), buf[:, f_ok:f_ok + 4].view(torch.int32)[:, 0])
-        c_score, c_row, c_tok, nxt_tok, nxt_row, ok = fields(log_buf)
-        tb = rules.timestamp_begin if rules is not None else 1 << 30
-        sampled = list(prefix[begin_index:]) if begin_index < len(prefix) else []
-        tsl = [t for t in sampled if t >= tb]
-        ts0 = [len(sampled), sampled[-1] if sampled else -1, sampled[-2] if len(sampled) > 1 else -1,
-               tsl[-1] if tsl else -1]
-        ts_state = torch.tensor([ts0] * rows, dtype=torch.int32, device=dev)
-        st = torch.tensor([list(rules.state(sampled)) if rules is not None else [0, 1, 0, 1]] * rows,
-                          dtype=torch.int32, device=dev)
-        tsb = torch.empty((rows, self.vocab), dtype=torch.float32, device=dev) if rules is not None else None
+        w = _BeamWindow(self, 0, 0, prefix, num_beams, k, eos, max_length, rules, begin_index, decoder_prompt_len,
+                        length_penalty)
         stream = _lib.stream_handle()
         self.prefill(prefix)
-        pos = len(prefix)
-        s = 0
-        replayed = 0
-
-        def replay(upto):
-            nonlocal replayed
-            if upto <= replayed:
-                return
-            cs, cr, ct, nt, nr, okh = (t.numpy() for t in fields(log_buf[replayed:upto].cpu()))
-            for i in range(upto - replayed):
-                toks, par = bp.process([(float(cs[i, j]), int(cr[i, j]), int(ct[i, j])) for j in range(k)])
-                if not bp.finished and (not okh[i] or toks != nt[i].tolist() or par != nr[i].tolist()):
-                    raise RuntimeError("GPU beam bookkeeping diverged from the host replay")
-                if bp.finished:
+        with torch.cuda.device(self.device):
+            while not w.bp.finished:
+                w.score(bias_at, stream)
+                if w.stopped:
                     break
-            replayed = upto
-
-        with torch.cuda.device(dev):
-            while True:
-                b = bias_at(pos)
-                if rules is not None and pos >= begin_index:
-                    _lib.check(self.lib.cbw_timestamp_rules(self._logits.data_ptr(), rows, self.vocab, self.vpad,
-                                                            _lib.ptr(b), st.data_ptr(), rules.timestamp_begin,
-                                                            rules.no_timestamps, rules.eos, rules.max_initial,
-                                                            tsb.data_ptr(), stream), "cbw_timestamp_rules")
-                    bias, bias_ld = tsb, self.vocab
-                else:
-                    bias, bias_ld = b, 0
-                _lib.check(self.lib.cbw_logprob_topk(self._logits.data_ptr(), rows, self.vocab, self.vpad,
-                                                     _lib.ptr(bias), bias_ld, k, lp.data_ptr(), idx.data_ptr(),
-                                                     stream), "cbw_logprob_topk")
-                # the next tokens / parent rows go straight into this step's log rows, which the reorder and
-                # the decode step then read (no per-token copies)
-                tok_s, row_s = nxt_tok[s].data_ptr(), nxt_row[s].data_ptr()
-                _lib.check(self.lib.cbw_beam_select(lp.data_ptr(), idx.data_ptr(), rows, k, eos, scores.data_ptr(),
-                                                    c_score[s].data_ptr(), c_row[s].data_ptr(), c_tok[s].data_ptr(),
-                                                    tok_s, row_s, ok[s].data_ptr(),
-                                                    ts_state.data_ptr(), st.data_ptr(), tb,
-                                                    int(rules is not None and pos >= begin_index), stream),
-                           "cbw_beam_select")
-                s += 1
-                if pos + 1 >= max_length:
-                    break
-                _lib.check(self.lib.cbw_decoder_reorder(self.h, row_s, rows, Benc, pos,
+                _lib.check(self.lib.cbw_decoder_reorder(self.h, w.next_rows().data_ptr(), rows, Benc, w.pos,
                                                         self._state.data_ptr(), self._state.numel(), stream),
                            "cbw_decoder_reorder")
-                _lib.check(self.lib.cbw_decoder_step(self.h, tok_s, pos, rows, Benc,
+                _lib.check(self.lib.cbw_decoder_step(self.h, w.next_tokens().data_ptr(), w.pos, rows, Benc,
                                                      self._state.data_ptr(), self._state.numel(),
                                                      self._logits.data_ptr(), stream), "cbw_decoder_step")
-                pos += 1
-                if s - replayed >= check_every:
-                    replay(s)
-                    if bp.finished:
-                        break
-            if not bp.finished:
-                replay(s)
-        if not bp.finished:
-            raise RuntimeError("GPU beam search ended before the host replay finished")
-        seq = bp.result()
-        return (seq, bp.score) if return_score else seq
+                w.pos += 1
+                if w.s - w.replayed >= check_every:
+                    w.replay()
+            w.replay()   # what is logged since the last replay (nothing when that one found the end)
+        return w.result(return_score)
 
     def beam_search_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], num_beams: int, eos: int,
                             max_length: int, bias_at: callable, rules=None, begin_index: int = 0,
                             decoder_prompt_len: int = 1, length_penalty: float = 1.0, check_every: int = 8,
                             return_score: bool = False) -> List:
-        """beam_search_dev for several windows at once (the windows of one iteration of the batched long-form loop,
-        pba_whisper.py:425-442: HF 4.37.2 runs their beam searches as one batch, each batch element's scorer
-        independent of the others): windows = [(enc_out f32 [1500, D] post-LN, decoder prefix)], decoded in lock step
+        """Beam search with the bookkeeping on the GPU for several windows at once (the windows of one iteration of the
+        batched long-form loop, pba_whisper.py:425-442: HF 4.37.2 runs their beam searches as one batch, each batch
+        element's scorer independent of the others): windows = [(enc_out f32 [1500, D] post-LN, decoder prefix)], decoded in lock step
         on one decoder state of ``16 // num_beams`` slots -- every row at its own position, each window on its own
         encoder slot (cbw_decoder_step_rows), windows admitted into slots as earlier ones finish.  Each window's
-        bookkeeping is beam_search_dev's (cbw_beam_select, replayed on the host every ``check_every`` steps) and each
-        row's logits equal a step over its window alone, so every window gets the tokens beam_search_dev gives it.
+        bookkeeping is one _BeamWindow (cbw_beam_select, replayed on the host every ``check_every`` steps), as in
+        beam_search_dev, and each row's logits equal a step over its window alone, so every window gets the tokens
+        beam_search_dev gives it.
         Returns the sequences (with ``return_score``: (sequence, score) pairs) in window order."""
         if max_length > self.max_len:
             raise ValueError(f"max_length {max_length} exceeds the decoder's {self.max_len} positions")
@@ -322,17 +264,14 @@ class DecoderEngine:
             tok = torch.zeros((rows,), dtype=torch.int32, device=self.device)
             ident = torch.arange(rows, dtype=torch.int32, device=self.device)
             src_rows = ident.clone()
-            active: List[Optional[_WindowSearch]] = [None] * slots
+            active: List[Optional[_BeamWindow]] = [None] * slots
             pending = list(range(len(windows)))
 
             def retire(w):
                 inc[w.r0:w.r0 + num_beams].fill_(0)
                 src_rows[w.r0:w.r0 + num_beams].copy_(ident[w.r0:w.r0 + num_beams])
                 active[w.slot] = None
-                if not w.bp.finished:
-                    raise RuntimeError("GPU beam search ended before the host replay finished")
-                seq = w.bp.result()
-                results[w.index] = (seq, w.bp.score) if return_score else seq
+                results[w.index] = w.result(return_score)
 
             it = 0
             while pending or any(a is not None for a in active):
@@ -342,15 +281,15 @@ class DecoderEngine:
                         enc_out, prefix = windows[i]
                         self.set_window(slot, enc_out)
                         self.prefill_window(slot, num_beams, prefix)
-                        active[slot] = _WindowSearch(i, slot, prefix, num_beams, k, eos, max_length, rules, begin_index,
-                                                     decoder_prompt_len, length_penalty, self.device, self.vocab)
+                        active[slot] = _BeamWindow(self, i, slot, prefix, num_beams, k, eos, max_length, rules,
+                                                   begin_index, decoder_prompt_len, length_penalty)
                         inc[slot * num_beams:(slot + 1) * num_beams].fill_(1)
                 live = [w for w in active if w is not None]
                 for w in live:
-                    w.score(self, bias_at, stream)
+                    w.score(bias_at, stream)
                     if not w.stopped:   # the step's tokens and (global) parent rows for this window's rows
-                        tok[w.r0:w.r0 + num_beams].copy_(w.views[3][w.s - 1])
-                        torch.add(w.views[4][w.s - 1], w.r0, out=src_rows[w.r0:w.r0 + num_beams])
+                        tok[w.r0:w.r0 + num_beams].copy_(w.next_tokens())
+                        torch.add(w.next_rows(), w.r0, out=src_rows[w.r0:w.r0 + num_beams])
                 for w in live:   # windows at max_length: replayed now, no further steps
                     if w.stopped:
                         w.replay()
@@ -718,25 +657,32 @@ def free_position_state(rules) -> Tuple[int, int, int, int]:
     return (0, 1, int(rules.timestamp_begin), 0)
 
 
-class _WindowSearch:
-    """One window's beam search inside DecoderEngine.beam_search_windows: its HF 4.37.2 BeamProcess, the device log
-    rows cbw_beam_select writes (one row per step: candidate scores / rows / tokens, next tokens, next parent rows,
-    ok flag) and the timestamp-rule state of its rows -- beam_search_dev's per-window state."""
+class _BeamWindow:
+    """One window's beam search with the bookkeeping on the GPU, the only statement of it: DecoderEngine.beam_search_dev
+    runs one (slot 0 of a start() state, stepped by cbw_decoder_step), beam_search_windows one per slot of its lock-step
+    state (cbw_decoder_step_rows).  Holds the window's HF 4.37.2 BeamProcess, the device log cbw_beam_select writes (one
+    row per step: candidate scores / rows / tokens, next tokens, next parent rows, ok flag) and the timestamp-rule
+    state of its rows.  ``score`` enqueues one step's choice, ``replay`` reads the new log rows back in one copy and
+    runs them through the BeamProcess, ``result`` is the search's outcome; the caller steps the decoder and advances
+    ``pos``."""
 
-    def __init__(self, index, slot, prefix, beams, k, eos, max_length, rules, begin_index, decoder_prompt_len,
-                 length_penalty, dev, vocab):
+    def __init__(self, eng: "DecoderEngine", index, slot, prefix, beams, k, eos, max_length, rules, begin_index,
+                 decoder_prompt_len, length_penalty):
         from .generate import BeamProcess
-        self.index, self.slot, self.r0, self.beams, self.k = index, slot, slot * beams, beams, k
+        dev = eng.device
+        self.eng, self.index, self.slot, self.r0, self.beams, self.k = eng, index, slot, slot * beams, beams, k
         self.eos, self.max_length, self.rules, self.begin = eos, max_length, rules, begin_index
         self.bp = BeamProcess(prefix, beams, eos, max_length, length_penalty, decoder_prompt_len)
         n_max = max(1, max_length - len(prefix))
         self.lp = torch.empty((beams, k), dtype=torch.float32, device=dev)
         self.idx = torch.empty((beams, k), dtype=torch.int32, device=dev)
         self.scores = torch.tensor([0.0] + [-1e9] * (beams - 1), dtype=torch.float64, device=dev)
+        # one log row per step, every field a column range of one byte buffer, so a replay is ONE device -> host
+        # copy (six separate .cpu() calls cost ~33 copy launches per replay)
         self.f = (0, 8 * k, 12 * k, 16 * k, 16 * k + 4 * beams, 16 * k + 8 * beams)
         row_bytes = (self.f[5] + 4 + 7) // 8 * 8
         self.log = torch.zeros((n_max, row_bytes), dtype=torch.uint8, device=dev)
-        self.views = self.fields(self.log)   # (scores, rows, tokens, next tokens, next rows, ok) column views
+        self.c_score, self.c_row, self.c_tok, self.nxt_tok, self.nxt_row, self.ok = self.fields(self.log)
         self.tb = rules.timestamp_begin if rules is not None else 1 << 30
         sampled = list(prefix[begin_index:]) if begin_index < len(prefix) else []
         tsl = [t for t in sampled if t >= self.tb]
@@ -745,46 +691,53 @@ class _WindowSearch:
         self.ts_state = torch.tensor([ts0] * beams, dtype=torch.int32, device=dev)
         self.st = torch.tensor([list(rules.state(sampled)) if rules is not None else [0, 1, 0, 1]] * beams,
                                dtype=torch.int32, device=dev)
-        self.tsb = torch.empty((beams, vocab), dtype=torch.float32, device=dev) if rules is not None else None
+        self.tsb = torch.empty((beams, eng.vocab), dtype=torch.float32, device=dev) if rules is not None else None
         self.pos = len(prefix)
-        self.s = 0
-        self.replayed = 0
+        self.s = 0           # log rows written
+        self.replayed = 0    # log rows the host has replayed
         self.stopped = False   # reached max_length: no further steps
 
     def fields(self, buf):
+        """(candidate scores, rows, tokens, next tokens, next parent rows, ok) column views of log rows"""
         f = self.f
         return (buf[:, f[0]:f[1]].view(torch.float64), buf[:, f[1]:f[2]].view(torch.int32),
                 buf[:, f[2]:f[3]].view(torch.int32), buf[:, f[3]:f[4]].view(torch.int32),
                 buf[:, f[4]:f[5]].view(torch.int32), buf[:, f[5]:f[5] + 4].view(torch.int32)[:, 0])
 
-    def score(self, eng: "DecoderEngine", bias_at, stream):
-        """this window's scores -> next beams (its log row self.s), as beam_search_dev's loop body"""
-        lib, nb, k = eng.lib, self.beams, self.k
+    def next_tokens(self) -> torch.Tensor:
+        """The step just scored: its rows' next tokens (device int32 [beams], a view of the log row)."""
+        return self.nxt_tok[self.s - 1]
+
+    def next_rows(self) -> torch.Tensor:
+        """The step just scored: its rows' parent rows within the window (device int32 [beams], as next_tokens)."""
+        return self.nxt_row[self.s - 1]
+
+    def score(self, bias_at, stream):
+        """This window's logits (its rows of the engine's step logits) -> scores -> next beams, into log row self.s:
+        the next tokens / parent rows go straight there, where the reorder and the decode step can read them."""
+        eng, nb, s = self.eng, self.beams, self.s
         b = bias_at(self.pos)
-        lg = eng._logits[self.r0]
+        lg = eng._logits[self.r0].data_ptr()
         ts_on = self.rules is not None and self.pos >= self.begin
         if ts_on:
-            r = self.rules
-            _lib.check(lib.cbw_timestamp_rules(lg.data_ptr(), nb, eng.vocab, eng.vpad, _lib.ptr(b), self.st.data_ptr(),
-                                               r.timestamp_begin, r.no_timestamps, r.eos, r.max_initial,
-                                               self.tsb.data_ptr(), stream), "cbw_timestamp_rules")
+            eng._timestamp_rules(lg, nb, b, self.st, self.rules, self.tsb, stream)
             bias, bias_ld = self.tsb, eng.vocab
         else:
             bias, bias_ld = b, 0
-        _lib.check(lib.cbw_logprob_topk(lg.data_ptr(), nb, eng.vocab, eng.vpad, _lib.ptr(bias), bias_ld, k,
-                                        self.lp.data_ptr(), self.idx.data_ptr(), stream), "cbw_logprob_topk")
-        c_score, c_row, c_tok, nxt_tok, nxt_row, ok = self.views
-        s = self.s
-        _lib.check(lib.cbw_beam_select(self.lp.data_ptr(), self.idx.data_ptr(), nb, k, self.eos, self.scores.data_ptr(),
-                                       c_score[s].data_ptr(), c_row[s].data_ptr(), c_tok[s].data_ptr(),
-                                       nxt_tok[s].data_ptr(), nxt_row[s].data_ptr(), ok[s].data_ptr(),
-                                       self.ts_state.data_ptr(), self.st.data_ptr(), self.tb, int(ts_on), stream),
+        eng._logprob_topk(lg, nb, bias, bias_ld, self.k, self.lp, self.idx, stream)
+        _lib.check(eng.lib.cbw_beam_select(self.lp.data_ptr(), self.idx.data_ptr(), nb, self.k, self.eos,
+                                           self.scores.data_ptr(), self.c_score[s].data_ptr(),
+                                           self.c_row[s].data_ptr(), self.c_tok[s].data_ptr(),
+                                           self.nxt_tok[s].data_ptr(), self.nxt_row[s].data_ptr(),
+                                           self.ok[s].data_ptr(), self.ts_state.data_ptr(), self.st.data_ptr(),
+                                           self.tb, int(ts_on), stream),
                    "cbw_beam_select")
         self.s += 1
         if self.pos + 1 >= self.max_length:
             self.stopped = True
 
     def replay(self):
+        """The log rows written since the last replay, in one device -> host copy, through the BeamProcess."""
         if self.s <= self.replayed:
             return
         cs, cr, ct, nt, nr, okh = (t.numpy() for t in self.fields(self.log[self.replayed:self.s].cpu()))
@@ -795,3 +748,10 @@ class _WindowSearch:
             if self.bp.finished:
                 break
         self.replayed = self.s
+
+    def result(self, return_score: bool = False):
+        """The finished search's sequence (prefix included), with ``return_score`` (sequence, its score)."""
+        if not self.bp.finished:
+            raise RuntimeError("GPU beam search ended before the host replay finished")
+        seq = self.bp.result()
+        return (seq, self.bp.score) if return_score else seq

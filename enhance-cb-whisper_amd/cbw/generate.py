@@ -144,6 +144,19 @@ class BeamProcess:
         return rows[0] if num_return_sequences == 1 else rows
 
 
+def _consume_prefix(fn, prefix: Sequence[int], rows: int):
+    """The forced prefix: every one of ``rows`` rows consumes prefix[t] at position t, so all rows stay identical -- in
+    one pass through ``fn.prefill(prefix)`` when the step function offers one and the prefix has more than one token
+    (its output at the intermediate positions is unused), token by token when there is none or it returns None (it
+    cannot run the pass).  -> (fn's output for position len(prefix), that position)."""
+    pre = getattr(fn, "prefill", None)
+    out = pre(list(prefix)) if pre is not None and len(prefix) > 1 else None
+    if out is None:
+        for t in range(len(prefix)):
+            out = fn([prefix[t]] * rows, t, None)
+    return out, len(prefix)
+
+
 def beam_search(step_fn: StepFn, prefix: Sequence[int], num_beams: int, eos: int, max_length: int,
                 length_penalty: float = 1.0, decoder_prompt_len: int = 1, pad: Optional[int] = None,
                 return_score: bool = False, forced: Optional[Dict[int, int]] = None, num_return_sequences: int = 1):
@@ -153,19 +166,7 @@ def beam_search(step_fn: StepFn, prefix: Sequence[int], num_beams: int, eos: int
     ``num_return_sequences`` > 1: the best that many (BeamProcess.result), a list of equal-length sequences."""
     forced = forced or {}
     bp = BeamProcess(prefix, num_beams, eos, max_length, length_penalty, decoder_prompt_len)
-    # forced prefix: every row consumes prefix[t] at position t; all rows stay identical -- in one
-    # prefill pass when the step function offers one (its logits at the intermediate positions are unused)
-    pos = 0
-    lp = idx = None
-    pre = getattr(step_fn, "prefill", None)
-    out = pre(list(prefix)) if pre is not None and len(prefix) > 1 else None
-    if out is not None:
-        lp, idx = out
-        pos = len(prefix)
-    else:
-        for t in range(len(prefix)):
-            lp, idx = step_fn([prefix[t]] * num_beams, pos, None)
-            pos += 1
+    (lp, idx), pos = _consume_prefix(step_fn, prefix, num_beams)
     while True:
         cand = bp.forced_candidates(forced[bp.cur_len]) if bp.cur_len in forced else bp.candidates(lp, idx)
         next_tokens, next_rows = bp.process(cand)
@@ -184,17 +185,7 @@ def greedy(step_fn: StepFn, prefix: Sequence[int], eos: int, max_length: int,
     """Greedy search from ``prefix``; ``forced`` as in ``beam_search``."""
     forced = forced or {}
     seq = list(prefix)
-    pos = 0
-    lp = idx = None
-    pre = getattr(step_fn, "prefill", None)
-    out = pre(list(prefix)) if pre is not None and len(prefix) > 1 else None
-    if out is not None:
-        lp, idx = out
-        pos = len(prefix)
-    else:
-        for t in range(len(prefix)):
-            lp, idx = step_fn([prefix[t]], pos, None)
-            pos += 1
+    (lp, idx), pos = _consume_prefix(step_fn, prefix, 1)
     while len(seq) < max_length:
         tok = forced.get(len(seq), int(idx[0, 0]))
         seq.append(tok)
@@ -273,17 +264,7 @@ def beam_sample(scores_fn, prefix: Sequence[int], num_beams: int, eos: int, max_
     if warp_order not in ("4.37", "5.x"):
         raise ValueError(f"warp_order {warp_order!r}: '4.37' or '5.x'")
     bp = BeamProcess(prefix, num_beams, eos, max_length, length_penalty, decoder_prompt_len)
-    pos = 0
-    scores = None
-    pre = getattr(scores_fn, "prefill", None)
-    if pre is not None and len(prefix) > 1:
-        scores = pre(list(prefix))
-        pos = len(prefix)
-    if scores is None:
-        pos = 0
-        for t in range(len(prefix)):
-            scores = scores_fn([prefix[t]] * num_beams, pos, None)
-            pos += 1
+    scores, pos = _consume_prefix(scores_fn, prefix, num_beams)
     while True:
         V = scores.shape[-1]
         bs = torch.as_tensor(bp.beam_scores, dtype=torch.float32, device=scores.device)[:, None]

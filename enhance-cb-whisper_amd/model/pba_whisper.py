@@ -26,6 +26,7 @@ from __future__ import annotations
 import os
 import warnings
 
+from functools import partial
 from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
@@ -45,6 +46,12 @@ def _dev_greedy() -> bool:
     """CBW_DEV_GREEDY, read at call time: greedy search with the token choice on the GPU (DecoderEngine.greedy_dev /
     greedy_windows) instead of the host loop over step_fn; 0 switches it off."""
     return os.environ.get("CBW_DEV_GREEDY", "1") != "0"
+
+
+def _dev_beam() -> bool:
+    """CBW_DEV_BEAM, read at call time: beam search with the bookkeeping on the GPU (DecoderEngine.beam_search_dev /
+    beam_search_windows) instead of the host scorer over step_fn; 0 switches it off."""
+    return os.environ.get("CBW_DEV_BEAM", "1") != "0"
 
 
 def _dev_sample() -> bool:
@@ -177,6 +184,17 @@ class PBAWhisper:
         ml = self._controls.get("max_length")
         return self.max_length if ml is None else min(self.max_length, int(ml))
 
+    def _window_setup(self, prefix: Sequence[int], max_new_tokens: Optional[int], free: Optional[Dict] = None):
+        """What every window decode starts from -> (max_length, begin_pos, bias, bias_begin, bias_at): the window's
+        max_length (``free``: its free and forced positions count as prefix), the first position after the forced ids
+        (begin suppression, the timestamp rules' begin index), the suppression biases, and bias_at(pos) = the bias of
+        a position (bias_begin at begin_pos)."""
+        n_forced = 1 + len(free["forced"]) if free else 0
+        max_length = self._window_max_length(len(prefix) + n_forced, max_new_tokens)
+        begin_pos = free["begin"] if free else len(prefix)
+        bias, bias_begin = self._biases()
+        return max_length, begin_pos, bias, bias_begin, lambda pos: bias_begin if pos == begin_pos else bias
+
     def encode(self, mel_packed: torch.Tensor) -> torch.Tensor:
         """post-LN encoder output f32 [B, 1500, D] (hidden_states[-1])."""
         return self.encoder.hidden_states(mel_packed, [self.encoder.n_layers], normalize=False)[:, 0]
@@ -198,11 +216,7 @@ class PBAWhisper:
         search): (sequence, HF's sequences_scores of it).  ``free`` (``_free_language``): ``prefix`` ends at
         <|startoftranscript|>, the next position is the search's, then ``free["forced"]``; begin suppression and the
         timestamp rules start at ``free["begin"]`` (short-form ``language=None``, host bookkeeping)."""
-        n_forced = 1 + len(free["forced"]) if free else 0
-        max_length = self._window_max_length(len(prefix) + n_forced, max_new_tokens)
-        begin_pos = free["begin"] if free else len(prefix)
-        bias, bias_begin = self._biases()
-        bias_at = lambda pos: bias_begin if pos == begin_pos else bias   # noqa: E731
+        max_length, begin_pos, bias, bias_begin, bias_at = self._window_setup(prefix, max_new_tokens, free)
         rows = max(1, num_beams)
         rules = self.rules if timestamps else None
         c = self._controls
@@ -213,28 +227,26 @@ class PBAWhisper:
             return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin, rules)
         self.decoder.start(enc_out, rows)
         lp, nrs = c.get("length_penalty", 1.0), c.get("num_return_sequences", 1)
+        # the host beam search every branch below runs, over that branch's step function
+        host_beams = partial(beam_search, prefix=prefix, num_beams=num_beams, eos=self.tokens.eot,
+                             max_length=max_length, length_penalty=lp, decoder_prompt_len=decoder_prompt_len,
+                             return_score=return_score)
         if c.get("repetition_penalty") is not None or c.get("no_repeat_ngram_size"):
             # a caller's multiplicative / n-gram processors: scores formed with torch ops on the device logits
             step = self.decoder.processed_step_fn(2 * rows, bias_at, c.get("repetition_penalty"),
                                                   c.get("no_repeat_ngram_size") or 0, greedy=num_beams <= 1)
             if num_beams <= 1:
                 return greedy(step, prefix, self.tokens.eot, max_length)
-            return beam_search(step, prefix, num_beams, self.tokens.eot, max_length, length_penalty=lp,
-                               decoder_prompt_len=decoder_prompt_len, return_score=return_score,
-                               num_return_sequences=nrs)
+            return host_beams(step, num_return_sequences=nrs)
         if free:
             step = self.decoder.step_fn(min(16, 2 * rows), bias_at, rules, begin_pos, free_pos=len(prefix))
             if num_beams <= 1:
                 return greedy(step, prefix, self.tokens.eot, max_length, forced=free["forced"])
-            return beam_search(step, prefix, num_beams, self.tokens.eot, max_length, length_penalty=lp,
-                               decoder_prompt_len=decoder_prompt_len, return_score=return_score, forced=free["forced"],
-                               num_return_sequences=nrs)
+            return host_beams(step, forced=free["forced"], num_return_sequences=nrs)
         if num_beams > 1 and nrs > 1:
             step = self.decoder.step_fn(min(16, 2 * rows), bias_at, rules, begin_pos)
-            return beam_search(step, prefix, num_beams, self.tokens.eot, max_length, length_penalty=lp,
-                               decoder_prompt_len=decoder_prompt_len, return_score=return_score,
-                               num_return_sequences=nrs)
-        if num_beams > 1 and os.environ.get("CBW_DEV_BEAM", "1") != "0":
+            return host_beams(step, num_return_sequences=nrs)
+        if num_beams > 1 and _dev_beam():
             # the bookkeeping on the GPU, no host round trip per token (cbw_beam_select; same result as below)
             out = self.decoder.beam_search_dev(prefix, num_beams, self.tokens.eot, max_length, min(16, 2 * rows),
                                                bias_at, rules, begin_pos, decoder_prompt_len, length_penalty=lp,
@@ -244,8 +256,7 @@ class PBAWhisper:
         step = self.decoder.step_fn(min(16, 2 * rows), bias_at, rules, begin_pos)
         if num_beams <= 1:
             return greedy(step, prefix, self.tokens.eot, max_length)
-        return beam_search(step, prefix, num_beams, self.tokens.eot, max_length, length_penalty=lp,
-                           decoder_prompt_len=decoder_prompt_len, return_score=return_score)
+        return host_beams(step)
 
     def sample_window(self, enc_out: torch.Tensor, prefix: List[int], temperature: float,
                       generator: Optional[torch.Generator], max_new_tokens: Optional[int] = None,
@@ -258,11 +269,7 @@ class PBAWhisper:
         For a seed it gives the tokens the host path (sample_search) draws, except where an fp32 tie in
         torch.multinomial's race resolves differently, and it leaves ``generator`` in the state the host path leaves
         it in."""
-        n_forced = 1 + len(free["forced"]) if free else 0
-        max_length = self._window_max_length(len(prefix) + n_forced, max_new_tokens)
-        begin_pos = free["begin"] if free else len(prefix)
-        bias, bias_begin = self._biases()
-        bias_at = lambda pos: bias_begin if pos == begin_pos else bias   # noqa: E731
+        max_length, begin_pos, bias, bias_begin, bias_at = self._window_setup(prefix, max_new_tokens, free)
         if not (temperature and temperature > 0) and not free and len(prefix) >= 2 and _dev_greedy():
             return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin,
                                            self.rules if timestamps else None, return_logprobs=True)
@@ -283,10 +290,7 @@ class PBAWhisper:
         reference's short-form GenerationMixin.generate call, pba_whisper.py:318-329): the decoder step and the
         processors' masks in libcbw, the warpers (temperature, top-k 50), the draw (torch.multinomial with
         ``generator``) and BeamSearchScorer's bookkeeping in cbw.generate.beam_sample."""
-        max_length = self._window_max_length(len(prefix), max_new_tokens)
-        begin_pos = len(prefix)
-        bias, bias_begin = self._biases()
-        bias_at = lambda pos: bias_begin if pos == begin_pos else bias   # noqa: E731
+        max_length, begin_pos, _, _, bias_at = self._window_setup(prefix, max_new_tokens)
         self.decoder.start(enc_out, num_beams)
         fn = self.decoder.scores_fn(bias_at, self.rules if timestamps else None, begin_pos)
         return beam_sample(fn, prefix, num_beams, self.tokens.eot, max_length, temperature, generator=generator,
@@ -642,9 +646,8 @@ class PBAWhisper:
 
         def decode(segs, prefixes, begin):
             enc = self.encode(self._pack(torch.cat(segs, 0)))
-            if num_beams > 1 and len(segs) > 1 and os.environ.get("CBW_DEV_BEAM", "1") != "0":
-                max_length = self._window_max_length(len(prefixes[0]), max_new_tokens)
-                bias_at = lambda pos: bias_begin if pos == begin else bias   # noqa: E731
+            if num_beams > 1 and len(segs) > 1 and _dev_beam():
+                max_length, _, _, _, bias_at = self._window_setup(prefixes[0], max_new_tokens)   # begin_pos == begin
                 return self.decoder.beam_search_windows([(enc[i], prefixes[i]) for i in range(len(segs))], num_beams,
                                                         self.tokens.eot, max_length, bias_at,
                                                         self.rules if timestamps else None, begin, begin,
