@@ -50,8 +50,13 @@ def test_teacher_forced_logits_vs_hf(golden_dir):
     np.testing.assert_allclose(lg, g["logits_last"], atol=2e-2 * np.abs(g["logits_last"]).max())
 
 
-def test_logprob_topk_kernel_exact():
+@pytest.mark.parametrize("split", [pytest.param(None, id="two-stage"), pytest.param("0", id="one-pass")])
+def test_logprob_topk_kernel_exact(monkeypatch, split):
     from cbw import _lib
+    if split is None:   # CBW_TOPK_SPLIT=0: the one-pass kernel (read on every call)
+        monkeypatch.delenv("CBW_TOPK_SPLIT", raising=False)
+    else:
+        monkeypatch.setenv("CBW_TOPK_SPLIT", split)
     lib = _lib.load()
     d = torch.device("cuda:0")
     g = torch.Generator(device=d).manual_seed(0)

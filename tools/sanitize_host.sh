@@ -15,7 +15,7 @@ SAN=(-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host
      -Xarch_host -fno-sanitize-recover=undefined)
 OBJS=()
 for f in conv_fp8.hip conv_fp8_stream.hip conv_igemm.hip conv_ring.hip conv_stream.hip gemv.hip bottleneck.hip \
-         kws_kernels.hip kws_exact.hip whisper_kernels.hip; do
+         kws_kernels.hip kws_exact.hip whisper_kernels.hip token_select.hip; do
   OBJS+=("$CSRC/build/$f.o")
   [ -f "$CSRC/build/$f.o" ] || { echo "missing $CSRC/build/$f.o: run the normal build first" >&2; exit 2; }
 done
