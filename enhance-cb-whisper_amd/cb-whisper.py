@@ -9,8 +9,9 @@ The reference hands the YAML to LightningCLI (``subclass_mode_model=True``), whi
 builds the same CBWhisper -- checkpoints are local HF-format directories (cbw.checkpoint).  The ACL/Aishell
 audio + transcript loaders (data/dataset.py) are dataset I/O, out of scope: ``--synthetic N`` runs N seeded
 30 s clips through ``test_step`` / ``on_test_epoch_end`` (mel -> spotting -> prompt -> beam search on the
-GPU) so the YAML -> model -> GPU path runs end to end; without it the runner builds the model and reports
-it.  ``fit``/``validate`` are training and out of scope.
+GPU) so the YAML -> model -> GPU path runs end to end (``--batch N``: in groups of N through ``test_step_batch``,
+the clips of a group decoded in lock step; 1, the default, is the clip-by-clip path); without it the runner builds
+the model and reports it.  ``fit``/``validate`` are training and out of scope.
 """
 from __future__ import annotations
 
@@ -29,13 +30,14 @@ if HERE not in sys.path:
 def main(argv=None):
     from cbw import cli
     argv = list(sys.argv[1:] if argv is None else argv)
-    own, overrides = cli.split_argv(argv, ("--config", "--synthetic", "--seed", "--max-new-tokens"))
+    own, overrides = cli.split_argv(argv, ("--config", "--synthetic", "--seed", "--max-new-tokens", "--batch"))
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("subcommand", choices=["test", "fit", "validate"])
     ap.add_argument("--config", required=True)
     ap.add_argument("--synthetic", type=int, default=0, help="run N seeded synthetic 30 s clips through test_step")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-new-tokens", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=1, help="synthetic clips per test_step_batch call (1: test_step)")
     sub = [a for a in overrides if not a.startswith("--")][:1]
     args = ap.parse_args(sub + own)
     overrides = [a for a in overrides if a not in sub]
@@ -57,18 +59,28 @@ def main(argv=None):
     from cbw import synth
     from cbw.whisper import log_mel
     if args.max_new_tokens is not None:   # bound the beam search of the synthetic run
-        gen = model.whisper.generate
+        gen, gen_b = model.whisper.generate, model.whisper.generate_batch
         model.whisper.generate = lambda *a, **k: gen(*a, max_new_tokens=args.max_new_tokens, **k)
+        model.whisper.generate_batch = lambda *a, **k: gen_b(*a, max_new_tokens=args.max_new_tokens, **k)
     model.on_test_epoch_start()
     n_mel = model.whisper.encoder_config[0]
     out = []
-    for i in range(args.synthetic):
+
+    def batch_of(i):
         clip = torch.from_numpy(synth.synth_clip(args.seed + i)).to(model.whisper.device)
         mel, _ = log_mel(clip, n_mel)
-        batch = {"utterance": {"features": mel[None], "attention_mask": None}, "transcript": "",
-                 "speaker": "synthetic", "hotword_labels": [torch.zeros(len(model.keywords), dtype=torch.long)]}
-        r = model.test_step(batch, i)
-        out.append({"clip": i, "spotted": model.last_spotted[0] if model.last_spotted else [], "pred": r["preds"]})
+        return {"utterance": {"features": mel[None], "attention_mask": None}, "transcript": "",
+                "speaker": "synthetic", "hotword_labels": [torch.zeros(len(model.keywords), dtype=torch.long)]}
+
+    for i0 in range(0, args.synthetic, max(1, args.batch)):
+        ids = list(range(i0, min(i0 + max(1, args.batch), args.synthetic)))
+        if args.batch <= 1:
+            rs = [model.test_step(batch_of(ids[0]), ids[0])]
+        else:
+            rs = model.test_step_batch([batch_of(i) for i in ids])
+        spotted = model.last_spotted or []
+        for j, (i, r) in enumerate(zip(ids, rs)):
+            out.append({"clip": i, "spotted": spotted[j] if j < len(spotted) else [], "pred": r["preds"]})
     print(json.dumps({"results": out}))
     return 0
 

@@ -123,6 +123,10 @@ SIGNATURES = {
                                 c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int,
                                                                 c_void_p]),
     "cbw_linear_rows_kernel": (c_char_p, [c_int, c_int, c_int, c_int]),
+    "cbw_linear_rows_wide": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                     c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                                                     c_int, c_void_p]),
+    "cbw_linear_rows_wide_kernel": (c_char_p, [c_int, c_int, c_int, c_int]),
     "cbw_layernorm_rows": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p]),
     "cbw_encoder_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "cbw_kws_profile": (c_int, [c_void_p, c_int]),
@@ -140,6 +144,7 @@ SIGNATURES = {
     "cbw_decoder_prefill_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64,
                                          c_void_p, c_void_p]),
     "cbw_decoder_step_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cbw_decoder_step_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "cbw_decoder_reorder": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "cbw_decoder_cross_attn_probs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                              c_int64, c_void_p, c_void_p]),

@@ -5,12 +5,40 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+
+
+WIDE_ROWS = 80   # CBW_DEC_WIDE_ROWS (cbw.h): the rows of one cbw_decoder_step_wide, 16 windows x 5 beams
+
+
+def dec_wide() -> bool:
+    """CBW_DEC_WIDE, read at call time: lock-step states of more than 16 rows (cbw_decoder_step_wide) where a caller
+    asks for them with ``max_rows``; 0 keeps 16 rows everywhere.  On by default: at 80 rows a row of the large-v3 step
+    costs 0.077 ms against 0.185 ms at 15 rows (docs/MEASUREMENT_LOG.md)."""
+    return os.environ.get("CBW_DEC_WIDE", "1") != "0"
+
+
+def row_cap(max_rows: int, beams: int = 1) -> int:
+    """The rows a lock-step state may have for a caller's ``max_rows``: 16, or up to WIDE_ROWS under CBW_DEC_WIDE when
+    the windows have at most 8 rows each (cbw_decoder_step_wide's limit)."""
+    if int(max_rows) <= 16 or beams > 8 or not dec_wide():
+        return min(16, max(1, int(max_rows)))
+    return min(WIDE_ROWS, int(max_rows))
+
+
+def _per_window(v, n: int, name: str) -> list:
+    """``v`` as one value per window: a list / tuple of n, or one value for all."""
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"{name}: one value per window, or one for all")
+        return list(v)
+    return [v] * n
 
 
 class DecoderEngine:
@@ -74,14 +102,18 @@ class DecoderEngine:
                        "cbw_decoder_cross_kv")
 
     # ------------------------------------------------------------------ several windows in one step
-    def start_windows(self, windows: int, beams: int):
+    def start_windows(self, windows: int, beams: int, max_rows: int = 16):
         """State for ``windows`` windows of ``beams`` rows each decoded in lock step (cbw_decoder_step_rows):
         window w's rows are [w beams, (w + 1) beams) and attend to encoder slot w; every row at its own position
-        (self._posr, device int32 [rows])."""
+        (self._posr, device int32 [rows]).  ``max_rows`` = 80 allows up to 80 rows (of at most 8 per window) and up
+        to 80 encoder slots, stepped by cbw_decoder_step_wide.  Memory: a slot's cross-attention K/V is n_layers x
+        1500 x d_model x 2 x 2 bytes (large-v3: 245 MB per window, 3.9 GB for 16, 19.7 GB for 80 one-row windows) and
+        a row's self-attention K/V n_layers x max_len x d_model x 2 x 2 bytes (large-v3: 73 MB, 5.9 GB at 80 rows)."""
         rows = windows * beams
+        cap = min(WIDE_ROWS, max(16, int(max_rows)))
         nb = self.lib.cbw_decoder_state_bytes(self.h, rows, windows)
-        if nb < 0 or rows > 16:
-            raise ValueError("windows x beams must be <= 16 rows")
+        if nb < 0 or rows > cap or (rows > 16 and beams > 8):
+            raise ValueError(f"windows x beams must be <= {cap} rows" + (", of <= 8 per window" if rows > 16 else ""))
         if self._state is None or self._state.numel() < nb:
             self._state = torch.empty(nb, dtype=torch.uint8, device=self.device)
         self._shape = (rows, windows)
@@ -114,9 +146,11 @@ class DecoderEngine:
     def step_rows(self, tokens: torch.Tensor):
         """One step of every row, row r at position self._posr[r] (tokens: device int32 [rows])."""
         rows, windows = self._shape
-        _lib.check(self.lib.cbw_decoder_step_rows(self.h, tokens.data_ptr(), self._posr.data_ptr(), rows, windows,
-                                                  self._state.data_ptr(), self._state.numel(), self._logits.data_ptr(),
-                                                  _lib.stream_handle()), "cbw_decoder_step_rows")
+        # more than 16 rows: the same step as row groups of 16 (cbw_decoder_step_wide), each row's bits unchanged
+        step, name = (self.lib.cbw_decoder_step_wide, "cbw_decoder_step_wide") if rows > 16 else \
+            (self.lib.cbw_decoder_step_rows, "cbw_decoder_step_rows")
+        _lib.check(step(self.h, tokens.data_ptr(), self._posr.data_ptr(), rows, windows, self._state.data_ptr(),
+                        self._state.numel(), self._logits.data_ptr(), _lib.stream_handle()), name)
         return self._logits[:, : self.vocab]
 
     def step(self, tokens: Sequence[int], pos: int) -> torch.Tensor:
@@ -239,26 +273,35 @@ class DecoderEngine:
     def beam_search_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], num_beams: int, eos: int,
                             max_length: int, bias_at: callable, rules=None, begin_index: int = 0,
                             decoder_prompt_len: int = 1, length_penalty: float = 1.0, check_every: int = 8,
-                            return_score: bool = False) -> List:
+                            return_score: bool = False, max_rows: int = 16) -> List:
         """Beam search with the bookkeeping on the GPU for several windows at once (the windows of one iteration of the
         batched long-form loop, pba_whisper.py:425-442: HF 4.37.2 runs their beam searches as one batch, each batch
         element's scorer independent of the others): windows = [(enc_out f32 [1500, D] post-LN, decoder prefix)], decoded in lock step
-        on one decoder state of ``16 // num_beams`` slots -- every row at its own position, each window on its own
-        encoder slot (cbw_decoder_step_rows), windows admitted into slots as earlier ones finish.  Each window's
+        on one decoder state of ``16 // num_beams`` slots (``max_rows`` = 80 under CBW_DEC_WIDE: ``80 // num_beams``,
+        see start_windows) -- every row at its own position, each window on its own
+        encoder slot (cbw_decoder_step_rows), windows admitted into slots as earlier ones finish.  ``max_length``,
+        ``begin_index``, ``decoder_prompt_len`` and ``bias_at`` may each be a list of one per window (the clips of a
+        batch differ in their prompts).  Each window's
         bookkeeping is one _BeamWindow (cbw_beam_select, replayed on the host every ``check_every`` steps), as in
         beam_search_dev, and each row's logits equal a step over its window alone, so every window gets the tokens
         beam_search_dev gives it.
         Returns the sequences (with ``return_score``: (sequence, score) pairs) in window order."""
-        if max_length > self.max_len:
-            raise ValueError(f"max_length {max_length} exceeds the decoder's {self.max_len} positions")
+        n = len(windows)
+        max_lengths = [int(m) for m in _per_window(max_length, n, "max_length")]
+        begins = _per_window(begin_index, n, "begin_index")
+        prompt_lens = _per_window(decoder_prompt_len, n, "decoder_prompt_len")
+        bias_ats = _per_window(bias_at, n, "bias_at")
+        if any(m > self.max_len for m in max_lengths):
+            raise ValueError(f"max_length {max(max_lengths)} exceeds the decoder's {self.max_len} positions")
         k = min(16, 2 * num_beams)
-        slots = max(1, min(len(windows), 16 // num_beams))
+        cap = row_cap(max_rows, num_beams)
+        slots = max(1, min(len(windows), cap // num_beams))
         if num_beams > 16 or any(len(p) < 2 for _, p in windows):
             raise ValueError("beam_search_windows needs num_beams <= 16 and prefixes of >= 2 tokens")
         stream = _lib.stream_handle()
         results: List = [None] * len(windows)
         with torch.cuda.device(self.device):
-            self.start_windows(slots, num_beams)
+            self.start_windows(slots, num_beams, cap)
             rows = slots * num_beams
             inc = torch.zeros((rows,), dtype=torch.int32, device=self.device)
             tok = torch.zeros((rows,), dtype=torch.int32, device=self.device)
@@ -281,12 +324,12 @@ class DecoderEngine:
                         enc_out, prefix = windows[i]
                         self.set_window(slot, enc_out)
                         self.prefill_window(slot, num_beams, prefix)
-                        active[slot] = _BeamWindow(self, i, slot, prefix, num_beams, k, eos, max_length, rules,
-                                                   begin_index, decoder_prompt_len, length_penalty)
+                        active[slot] = _BeamWindow(self, i, slot, prefix, num_beams, k, eos, max_lengths[i], rules,
+                                                   begins[i], prompt_lens[i], length_penalty)
                         inc[slot * num_beams:(slot + 1) * num_beams].fill_(1)
                 live = [w for w in active if w is not None]
                 for w in live:
-                    w.score(bias_at, stream)
+                    w.score(bias_ats[w.index], stream)
                     if not w.stopped:   # the step's tokens and (global) parent rows for this window's rows
                         tok[w.r0:w.r0 + num_beams].copy_(w.next_tokens())
                         torch.add(w.next_rows(), w.r0, out=src_rows[w.r0:w.r0 + num_beams])
@@ -315,12 +358,14 @@ class DecoderEngine:
 
     def greedy_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], eos: int, max_lengths,
                        bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules=None,
-                       check_every: int = 8, return_logprobs: bool = False, max_slots: int = 16) -> List:
+                       check_every: int = 8, return_logprobs: bool = False, max_slots: Optional[int] = None,
+                       max_rows: int = 16) -> List:
         """Greedy search (HF 4.37.2 greedy branch of GenerationMixin.generate, the call of pba_whisper.py:318-331 and
         :425-442 with num_beams = 1, do_sample = False) for several windows in lock step with no host round trip per
         token: windows = [(enc_out f32 [1500, D] post-LN, decoder prefix)], max_lengths one per window (or one int),
-        decoded on one decoder state of min(len(windows), 16, ``max_slots``) slots of one row each, built as
-        beam_search_windows builds its slots.  Per step one cbw_greedy_select over all rows (scores = logits + ``bias_begin`` at a window's
+        decoded on one decoder state of min(len(windows), 16, ``max_slots``) slots of one row each (``max_rows`` = 80
+        under CBW_DEC_WIDE: 80 in place of the 16), built as
+        beam_search_windows builds its slots.  Per step one cbw_greedy_select per 16 rows (scores = logits + ``bias_begin`` at a window's
         first free position, ``bias`` after it, + the timestamp rules of ``rules`` from a device-side state; argmax;
         log-prob of the processed scores) writes the step's row of a device log, cbw_decoder_step_rows reads its tokens
         from there, and the rows still active move one position.  Every ``check_every`` steps the new log rows come
@@ -329,16 +374,18 @@ class DecoderEngine:
         cache).  Begin suppression and the rules' begin index are len(prefix); no forced positions.
         Returns the sequences (prefix included) in window order; with ``return_logprobs`` (sequence, per-step
         log-probs) pairs."""
-        def select(args, live, stream):
+        def select(args, live, r0, stream):
             _lib.check(self.lib.cbw_greedy_select(*args, stream), "cbw_greedy_select")
         return self._lock_step("greedy_windows", windows, eos, max_lengths, bias, bias_begin, rules, select,
-                               check_every, return_logprobs, max_slots)
+                               check_every, return_logprobs, max_slots, max_rows=max_rows)
 
     def _lock_step(self, name: str, windows, eos: int, max_lengths, bias, bias_begin, rules, select: callable,
-                   check_every: int, return_logprobs: bool, max_slots: int, replayed: Optional[callable] = None) -> List:
+                   check_every: int, return_logprobs: bool, max_slots: Optional[int], replayed: Optional[callable] = None,
+                   max_rows: int = 16) -> List:
         """The lock-step driver greedy_windows and sample_windows share: slot admission, the device log of
         ``check_every`` steps, the one copy per replay, cbw.generate.greedy_replay and the divergence check.  Per step
-        ``select(args, live, stream)`` makes the rows' choice: ``args`` are the arguments cbw_greedy_select and
+        and slice of 16 rows starting at ``r0`` (those kernels take at most 16; every argument is row-indexed)
+        ``select(args, live, r0, stream)`` makes the rows' choice: ``args`` are the arguments cbw_greedy_select and
         cbw_sample_select have in common (logits ... logprob, writing the step's row of the log), ``live[slot]`` the
         window in each slot (None: empty).  ``replayed(window, taken, finished)`` is called after every replay with the
         number of logged steps the window took from it."""
@@ -365,8 +412,9 @@ class DecoderEngine:
         tb, no_ts, max_initial = (rules.timestamp_begin, rules.no_timestamps, rules.max_initial) if rules is not None \
             else (-1, -1, -1)
         with torch.cuda.device(dev):
-            slots = max(1, min(len(pending), 16, int(max_slots)))
-            self.start_windows(slots, 1)
+            cap = row_cap(max_rows)
+            slots = max(1, min(len(pending), cap, cap if max_slots is None else int(max_slots)))
+            self.start_windows(slots, 1, cap)
             ts_state = torch.zeros((slots, 4), dtype=torch.int32, device=dev)
             limit = torch.zeros((slots,), dtype=torch.int32, device=dev)
             active = torch.zeros((slots,), dtype=torch.int32, device=dev)
@@ -390,10 +438,14 @@ class DecoderEngine:
                 # no row needs more steps than the longest remainder; the step after the last of those is not run
                 left = max(limits[w] - len(seqs[s]) for s, w in enumerate(live) if w is not None)
                 steps = min(check_every, left)
+                lg, tsp, posp, limp, actp = (t.data_ptr() for t in (self._logits, ts_state, self._posr, limit, active))
                 for c in range(steps):
-                    select((self._logits.data_ptr(), slots, self.vocab, self.vpad, _lib.ptr(bias), _lib.ptr(bias_begin),
-                            tb, no_ts, eos, max_initial, ts_state.data_ptr(), self._posr.data_ptr(), limit.data_ptr(),
-                            active.data_ptr(), log[c, 0].data_ptr(), log_lp[c, 1].data_ptr()), live, stream)
+                    tokp, lpp = log[c, 0].data_ptr(), log_lp[c, 1].data_ptr()
+                    for r0 in range(0, slots, 16):
+                        o = 4 * r0   # int32 / f32 rows
+                        select((lg + o * self.vpad, min(16, slots - r0), self.vocab, self.vpad, _lib.ptr(bias),
+                                _lib.ptr(bias_begin), tb, no_ts, eos, max_initial, tsp + 4 * o, posp + o, limp + o,
+                                actp + o, tokp + o, lpp + o), live, r0, stream)
                     log[c, 2].copy_(active)
                     if c + 1 == left:
                         break
@@ -427,7 +479,8 @@ class DecoderEngine:
 
     def sample_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], eos: int, max_lengths,
                        bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules, temperature: float,
-                       generators, top_k: int = 50, check_every: int = 8, max_slots: int = 16) -> List:
+                       generators, top_k: int = 50, check_every: int = 8, max_slots: Optional[int] = None,
+                       max_rows: int = 16) -> List:
         """Temperature sampling (HF 4.37.2 sample branch of GenerationMixin.generate: the call of
         pba_whisper.py:318-331 with do_sample = True, and every temperature > 0 rung of generate_with_fallback,
         :425-442) for several windows in lock step with no host round trip per token: greedy_windows' driver with
@@ -450,22 +503,23 @@ class DecoderEngine:
         noise: List[Optional[torch.Tensor]] = [None]
         states: List[list] = [[] for _ in gens]   # per window: the generator's state after each draw since the last replay
 
-        def select(args, live, stream):
+        def select(args, live, r0, stream):
             if noise[0] is None:
                 noise[0] = torch.ones((len(live), V), dtype=torch.float32, device=self.device)
-            for slot, w in enumerate(live):
+            for slot in range(r0, min(r0 + 16, len(live))):   # the draws of this slice's windows, in slot order
+                w = live[slot]
                 if w is not None:
                     noise[0][slot].exponential_(generator=gens[w])
                     states[w].append(gens[w].get_state())
-            _lib.check(self.lib.cbw_sample_select(*args, float(temperature), int(top_k), noise[0].data_ptr(), V, stream),
-                       "cbw_sample_select")
+            _lib.check(self.lib.cbw_sample_select(*args, float(temperature), int(top_k),
+                                                  noise[0].data_ptr() + 4 * r0 * V, V, stream), "cbw_sample_select")
 
         def replayed(w, taken, finished):
             if finished:
                 gens[w].set_state(states[w][taken - 1])
             states[w].clear()
         return self._lock_step("sample_windows", windows, eos, max_lengths, bias, bias_begin, rules, select,
-                               check_every, True, max_slots, replayed)
+                               check_every, True, max_slots, replayed, max_rows=max_rows)
 
     def sample_dev(self, enc_out: torch.Tensor, prefix: Sequence[int], eos: int, max_length: int,
                    bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules, temperature: float,

@@ -63,10 +63,15 @@ struct GemvArgs {
     int kv_D;
     const int* kv_pos;   // optional: the append position read on the device (kv_k/kv_v then point at position 0)
     int kv_pos_rows;     // with kv_pos: 1 = one position per row (kv_pos[m], a step over several windows)
+    int wide_gx;         // cbw_gemv_wide only (it sets this): 1 = the row groups are grid x, 0 = grid y
 };
 int cbw_gemv_waves(int K);
 bool cbw_gemv_ln_ok(int M, int K);   // whether the LayerNorm prologue applies to this shape
 hipError_t cbw_gemv(const GemvArgs& a, hipStream_t st);
+// the same Linear over 1 <= M <= CBW_DEC_WIDE_ROWS (80) rows: ceil(M / 16) row groups in one launch, each the
+// 16-slot kernel of cbw_gemv's family on its rows, so a row carries the bits cbw_gemv gives it on its 16-row slice
+// (gemv_wide_route, gemv_route.h).  groups_fast: the groups are the fast grid coordinate, else the column blocks.
+hipError_t cbw_gemv_wide(const GemvArgs& a, hipStream_t st, bool groups_fast);
 
 // fp8 (OCP e4m3) implicit-GEMM conv (conv_fp8.hip): the first tier of the exact-decision cascade.  x / res / y
 // e4m3 NHWC with one static scale per tensor (folded into the weights / res_scale / y_inv_scale); w e4m3

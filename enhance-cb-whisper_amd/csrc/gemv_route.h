@@ -104,3 +104,32 @@ constexpr GemvRoute gemv_route(int M, int N, int K, bool ln) {
     r.name = ln ? "gemv_kernel<true>" : "gemv_kernel<false>";
     return r;
 }
+
+// ---- the wide launch (cbw_gemv_wide): 1 <= M <= GV_WIDE_ROWS rows as ceil(M / 16) row groups in one launch
+constexpr int GV_WIDE_ROWS = 80;   // = CBW_DEC_WIDE_ROWS (cbw.h): 16 windows x 5 beams
+
+struct GemvWideRoute {
+    // what every group runs: gemv_route(16, N, K, ln) -- the family of (K, ln), the tail group included on its 16-slot
+    // instantiation; group.grid = the column blocks, group.lds = the LDS of a full group
+    GemvRoute group;
+    int groups = 0;               // ceil(M / 16); 0 = no route
+    int grid_x = 0, grid_y = 0;   // groups_fast: (groups, column blocks), else (column blocks, groups)
+    // "gemv_wide_kernel<LN>" / "gemv_dot_wide_kernel<LN, NJ, CPW, 16, KS, 8>": the group's kernel text, compiled as a row group
+    const char* name = "";
+};
+
+constexpr GemvWideRoute gemv_wide_route(int M, int N, int K, bool ln, bool groups_fast = false) {
+    GemvWideRoute w;
+    if (M < 1 || M > GV_WIDE_ROWS) return w;
+    const GemvRoute r = gemv_route(16, N, K, ln);
+    if (r.kernel == GemvKernel::Invalid) return w;
+    w.group = r;
+    w.groups = (M + 15) / 16;
+    w.grid_x = groups_fast ? w.groups : r.grid;
+    w.grid_y = groups_fast ? r.grid : w.groups;
+    if (r.kernel == GemvKernel::Mfma) w.name = ln ? "gemv_wide_kernel<true>" : "gemv_wide_kernel<false>";
+    else if (ln) w.name = CBW_GD_NAME_NJ(r.nj, "gemv_dot_wide_kernel<true, ", ", 2, 16, 1, 8>");
+    else if (r.nj == 20) w.name = "gemv_dot_wide_kernel<false, 20, 1, 16, 2, 8>";
+    else w.name = CBW_GD_NAME_NJ(r.nj, "gemv_dot_wide_kernel<false, ", ", 2, 16, 1, 8>");
+    return w;
+}

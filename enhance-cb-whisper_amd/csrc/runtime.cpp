@@ -2644,6 +2644,8 @@ struct LinearRun {
     bool gemv, fuse;
     uint16_t* ln_out;
     float* splitk = nullptr;   // the encoder's split-K partial sums, for its residual Linears (out-projection, fc2)
+    // cbw_decoder_step_wide: the GEMV as row groups of 16 in one launch (cbw_gemv_wide), up to CBW_DEC_WIDE_ROWS rows
+    bool wide = false, wide_groups_fast = false;
 
     int lin(const ConvW& c, const void* x, void* y, const void* res, int flags) const {
         if (!gemv) return launch_conv(c, x, 1, 1, M, y, res, flags, zero, st, nullptr, nullptr, res ? splitk : nullptr);
@@ -2666,7 +2668,7 @@ struct LinearRun {
                                      ln ? 1e-5f : 0.f, c.w.p, c.b.as<float>(), res, res ? c.cout : 0, y, c.cout, M,
                                      c.cout, c.cin, flags | (c.relu ? CBW_EPI_RELU : 0), kv.k ? kv.k + at : nullptr,
                                      kv.k ? kv.v + at : nullptr, kv.ld, kv.D, kv.pos_dev, kv.pos_rows);
-        HIPCHK(cbw_gemv(g, st));
+        HIPCHK(wide ? cbw_gemv_wide(g, st, wide_groups_fast) : cbw_gemv(g, st));
         return CBW_OK;
     }
 };
@@ -2847,9 +2849,18 @@ bool dec_split_enabled() {   // CBW_DEC_SPLIT=0 runs the step's attention on the
     const char* e = getenv("CBW_DEC_SPLIT");
     return !(e && atoi(e) == 0);
 }
-bool dec_gemv_enabled(int B) {   // CBW_DEC_GEMV=0 runs the decode-step Linears on the tile kernels (A/B)
+// CBW_DEC_GEMV=0 runs the decode-step Linears on the tile kernels (A/B); max_rows: 16, or CBW_DEC_WIDE_ROWS where the
+// rows run as groups of 16 (cbw_gemv_wide)
+bool dec_gemv_enabled(int B, int max_rows = 16) {
     const char* e = getenv("CBW_DEC_GEMV");
-    return B <= 16 && !(e && atoi(e) == 0);
+    return B <= max_rows && !(e && atoi(e) == 0);
+}
+// CBW_GEMV_WIDE_ORDER=groups makes the row groups of a wide launch the fast grid coordinate (A/B; default: the
+// column blocks, docs/MEASUREMENT_LOG.md)
+static_assert(GV_WIDE_ROWS == CBW_DEC_WIDE_ROWS, "gemv_route.h / cbw.h");
+bool gemv_wide_groups_fast() {
+    const char* e = getenv("CBW_GEMV_WIDE_ORDER");
+    return e && !strcmp(e, "groups");
 }
 
 DecState dec_carve(const cbw_decoder* h, void* state, int B, int Benc) {
@@ -3026,8 +3037,9 @@ namespace {
 // one decode step; pos_dev (optional) = the position read on the device (pos is then unused): every launch
 // argument is then independent of the position, so the step can be captured once and replayed.  pos_rows: pos_dev
 // holds one position per row (the rows of several windows, each at its own position, in one step)
+// wide (cbw_decoder_step_wide): up to CBW_DEC_WIDE_ROWS rows, the Linears as row groups of 16 on the fused GEMV
 int dec_step(cbw_decoder* h, const int32_t* tokens, int pos, const int32_t* pos_dev, int B, int Benc, void* state,
-             int64_t state_bytes, float* logits, cbw_stream_t stream, int pos_rows = 0) {
+             int64_t state_bytes, float* logits, cbw_stream_t stream, int pos_rows = 0, bool wide = false) {
     CHK(dec_check(h, tokens && state && logits, B, Benc));
     if (!pos_dev && (pos < 0 || pos >= h->cfg.max_len)) return fail(CBW_ERR_INVALID, "step needs 0 <= pos < max_len");
     DecState s;
@@ -3037,8 +3049,10 @@ int dec_step(cbw_decoder* h, const int32_t* tokens, int pos, const int32_t* pos_
     // the step's Linears: skinny GEMV (gemv.hip) for <= 16 rows, else the implicit-GEMM tiles; LayerNorm -> Linear
     // pairs: on the GEMV the LayerNorm runs in its prologue (and the qkv projection appends K/V to the cache in its
     // epilogue), else as separate launches
-    const bool gemv = dec_gemv_enabled(B);
-    const LinearRun run{B, st, h->zero.p, gemv, gemv && dec_fuse_enabled() && cbw_gemv_ln_ok(B, D), s.a};
+    const bool gemv = dec_gemv_enabled(B, wide ? CBW_DEC_WIDE_ROWS : 16);
+    LinearRun run{B, st, h->zero.p, gemv, gemv && dec_fuse_enabled() && cbw_gemv_ln_ok(wide ? 16 : B, D), s.a};
+    run.wide = wide;
+    run.wide_groups_fast = wide && gemv_wide_groups_fast();
     if (pos_dev && !run.fuse)
         return fail(CBW_ERR_INVALID, "device-position steps need the fused GEMV path (<= 16 rows, CBW_DEC_GEMV / "
                                      "CBW_DEC_FUSE on)");
@@ -3083,6 +3097,16 @@ int cbw_decoder_step_rows(cbw_decoder* h, const int32_t* tokens, const int32_t* 
                           int64_t state_bytes, float* logits, cbw_stream_t stream) {
     if (!pos_rows) return fail(CBW_ERR_INVALID, "null pos_rows");
     return dec_step(h, tokens, 0, pos_rows, B, Benc, state, state_bytes, logits, stream, 1);
+}
+
+int cbw_decoder_step_wide(cbw_decoder* h, const int32_t* tokens, const int32_t* pos_rows, int B, int Benc, void* state,
+                          int64_t state_bytes, float* logits, cbw_stream_t stream) {
+    if (!pos_rows) return fail(CBW_ERR_INVALID, "null pos_rows");
+    if (B > CBW_DEC_WIDE_ROWS) return fail(CBW_ERR_INVALID, "cbw_decoder_step_wide: at most 80 rows");
+    // the split cross-attention reads a window's K/V once for its rows: at most 8 rows per encoder slot
+    if (B > 0 && Benc > 0 && B % Benc == 0 && B / Benc > 8)
+        return fail(CBW_ERR_INVALID, "cbw_decoder_step_wide: at most 8 rows per encoder slot");
+    return dec_step(h, tokens, 0, pos_rows, B, Benc, state, state_bytes, logits, stream, 1, true);
 }
 
 int cbw_decoder_prefill(cbw_decoder* h, const int32_t* tokens, int T, int B, int Benc, void* state,
@@ -3142,7 +3166,8 @@ int cbw_decoder_prefill_rows(cbw_decoder* h, const int32_t* tokens, int T, int s
     hipStream_t st = (hipStream_t)stream;
     CHK(dec_prefill_layers(h, tokens, T, slot, r0, nb, B, Benc, s, st));
     // logits of the last prefix token only: one row, its vocabulary projection on the same kernel as the step's
-    const LinearRun last{1, st, h->zero.p, dec_gemv_enabled(B), false, s.pa};
+    // (a state of more than 16 rows is stepped by cbw_decoder_step_wide, on the GEMV as well)
+    const LinearRun last{1, st, h->zero.p, dec_gemv_enabled(B, CBW_DEC_WIDE_ROWS), false, s.pa};
     return last.ln_lin(s.ph + (size_t)(T - 1) * h->cfg.d_model, h->lnf, h->emb, logits, CBW_EPI_OUT_F32);
 }
 
@@ -3432,6 +3457,30 @@ int cbw_linear_rows(const uint16_t* x, const float* xf, int ldx, const float* ln
 }
 
 const char* cbw_linear_rows_kernel(int M, int N, int K, int ln) { return gemv_route(M, N, K, ln != 0).name; }
+
+int cbw_linear_rows_wide(const uint16_t* x, const float* xf, int ldx, const float* ln_g, const float* ln_b, float ln_eps,
+                         const uint16_t* w, const float* bias, const void* res, int res_ld, void* y, int ldy, int M,
+                         int N, int K, int flags, uint16_t* kv_k, uint16_t* kv_v, int64_t kv_ld, int kv_D,
+                         const int32_t* kv_pos, int kv_pos_rows, cbw_stream_t stream) {
+    if ((!x && !xf) || !w || !y) return fail(CBW_ERR_INVALID, "cbw_linear_rows_wide: null operand");
+    if (M < 1 || M > CBW_DEC_WIDE_ROWS || N < 4 || N % 4 || K < 32 || K % 32 || ldx % 8 || ldy % 4 || ldx < K ||
+        ldy < N || (res && (res_ld % 4 || res_ld < N)))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows_wide: 1 <= M <= 80, K % 32, N % 4, ldx % 8, ldy % 4, res_ld % 4");
+    if (flags & ~(CBW_EPI_RELU | CBW_EPI_GELU | CBW_EPI_RES_F32 | CBW_EPI_OUT_F32 | CBW_EPI_RES_AFTER_ACT))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows_wide: unknown flag");
+    if (xf && (!ln_g || !ln_b || !cbw_gemv_ln_ok(16, K)))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows_wide: the LayerNorm prologue needs gamma, beta and K <= 1280");
+    if (kv_k && (!kv_v || kv_D <= 0 || kv_D % 4 || N != 3 * kv_D || kv_ld % 4 || kv_ld < kv_D || (flags & CBW_EPI_OUT_F32)))
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows_wide: K/V append needs kv_v, N == 3 kv_D, kv_D % 4, kv_ld % 4, bf16 output");
+    if (gemv_wide_route(M, N, K, xf != nullptr).groups < 1)
+        return fail(CBW_ERR_INVALID, "cbw_linear_rows_wide: no kernel for this shape");
+    HIPCHK(cbw_gemv_wide(gemv_args(x, xf, ldx, ln_g, ln_b, ln_eps, w, bias, res, res_ld, y, ldy, M, N, K, flags, kv_k,
+                                   kv_v, kv_ld, kv_D, kv_pos, kv_pos_rows),
+                         (hipStream_t)stream, gemv_wide_groups_fast()));
+    return CBW_OK;
+}
+
+const char* cbw_linear_rows_wide_kernel(int M, int N, int K, int ln) { return gemv_wide_route(M, N, K, ln != 0).name; }
 
 int cbw_layernorm_rows(const float* x, const float* g, const float* b, uint16_t* y, float* y32, int rows, int D,
                        float eps, cbw_stream_t stream) {

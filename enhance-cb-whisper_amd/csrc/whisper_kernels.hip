@@ -920,7 +920,7 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const bf16* __restri
 __global__ void dec_gather_rows_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst, const int* __restrict__ rows,
                                        int64_t row_elems, int64_t copy_elems) {
     const int r = blockIdx.y;
-    const bf16* s = src + (int64_t)rows[r] * row_elems;
+    const bf16* s = src + (int64_t)min(max(rows[r], 0), (int)gridDim.y - 1) * row_elems;   // clamped, as dec_reorder_kv_kernel
     bf16* d = dst + (int64_t)r * row_elems;
     for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 8; i < copy_elems; i += (int64_t)gridDim.x * blockDim.x * 8)
         *(bf16x8*)(d + i) = *(const bf16x8*)(s + i);

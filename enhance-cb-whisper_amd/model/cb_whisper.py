@@ -372,6 +372,10 @@ class CBWhisper:
                 keywords = [list(union) for _ in range(S)]
         else:
             keywords = [list(self.oracle_buffer) for _ in range(S)]
+        return self._keyword_prompts(keywords, start_of_prev)
+
+    def _keyword_prompts(self, keywords: List[List[str]], start_of_prev: bool) -> List[List[int]]:
+        """The prompt ids of each segment's (or clip's) keywords (cb_whisper.py:133-149); remembers them as last_spotted."""
         self.last_spotted = keywords
         ids = []
         for kwds in keywords:
@@ -382,6 +386,20 @@ class CBWhisper:
             ids.append(p if start_of_prev else p[1:])
         return ids
 
+    def _keyword_spotting_clips(self, oracles: Sequence[Sequence[str]]) -> Callable:
+        """The keyword_spotting callback of a batch of independent clips: every clip gets its OWN keywords -- those
+        spotted in it, or its own oracle list.  (The "union" of keyword_spotting is over the segments of one audio.)"""
+        def spot(input_features: torch.Tensor, start_of_prev: bool = False) -> List[List[int]]:
+            S = input_features.size(0)
+            if not self.prompt:
+                return [[] for _ in range(S)]
+            if self.oracle == "kws":
+                keywords = self.spot_keywords(input_features) if len(self.keywords) else [[] for _ in range(S)]
+            else:
+                keywords = [list(o) for o in oracles]
+            return self._keyword_prompts(keywords, start_of_prev)
+        return spot
+
     def forward(self, input_features: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 oracle: Sequence[str] = ()):
         """cb_whisper.py:151-187 (always short-form there: is_shortform tests dim 0)."""
@@ -391,7 +409,11 @@ class CBWhisper:
                                      condition_on_prev_tokens=False, return_segments=False,
                                      num_beams=self.num_beams, do_sample=False, temperature=0,
                                      keyword_spotting=self.keyword_spotting)
-        toks = pred[0].tolist()
+        return self._to_text(pred[0].tolist())
+
+    __call__ = forward
+
+    def _to_text(self, toks: List[int]):
         tok = getattr(self.whisper, "tokenizer", None)
         if self.detokenize is None and tok is not None:
             return tok.decode(toks, skip_special_tokens=True).strip()
@@ -400,26 +422,36 @@ class CBWhisper:
         special = set(range(self.whisper.tokens.eot, self.whisper.decoder_config[0]))
         return self.detokenize([t for t in toks if t not in special]).strip()
 
-    __call__ = forward
+    def transcribe_batch(self, input_features: torch.Tensor, oracles: Optional[Sequence[Sequence[str]]] = None) -> List:
+        """A batch of short clips [N, n_mel, T <= 3000] in one call (PBAWhisper.generate_batch): element i equals
+        ``forward(input_features[i:i + 1], oracle=oracles[i])``.  Every clip gets its own keywords."""
+        N = input_features.size(0)
+        oracles = [[] for _ in range(N)] if oracles is None else [list(o) for o in oracles]
+        if len(oracles) != N:
+            raise ValueError(f"transcribe_batch needs one oracle list per clip ({N}), got {len(oracles)}")
+        preds = self.whisper.generate_batch(input_features, task="transcribe", language=self.language,
+                                            return_timestamps=False, num_beams=self.num_beams,
+                                            keyword_spotting=self._keyword_spotting_clips(oracles))
+        self.oracle_buffer = list(oracles[-1]) if oracles else []   # where the loop of forward calls leaves it
+        return [self._to_text(p[0].tolist()) for p in preds]
 
     # ------------------------------------------------------------------ evaluation (cb_whisper.py:212-289)
     def on_test_epoch_start(self):
         self.test_step_outputs = []
 
-    def test_step(self, batch: dict, batch_idx: int = 0, rng: Optional[random.Random] = None):
-        """cb_whisper.py:218-242: the oracle keyword list (gold = the labelled keywords, random =
-        as many non-labelled ones, kws = none: the spotter runs), then forward."""
+    def _batch_oracle(self, batch: dict, rng: Optional[random.Random]) -> List[str]:
+        """cb_whisper.py:218-232: the oracle keyword list of a batch (gold = the labelled keywords, random = as many
+        non-labelled ones, kws = none: the spotter runs)."""
         labels = batch.get("hotword_labels")
         pos = [] if labels is None else torch.argwhere(torch.cat(list(labels), 0)).view(-1).tolist()
         if self.oracle == "gold":
-            oracle = [self.keywords[i] for i in pos]
-        elif self.oracle == "random":
+            return [self.keywords[i] for i in pos]
+        if self.oracle == "random":
             pool = sorted(set(range(len(self.keywords))) - set(pos))
-            oracle = [self.keywords[i] for i in (rng or random).sample(pool, len(pos))]
-        else:
-            oracle = []
-        preds = self.forward(input_features=batch["utterance"]["features"],
-                             attention_mask=batch["utterance"].get("attention_mask"), oracle=oracle)
+            return [self.keywords[i] for i in (rng or random).sample(pool, len(pos))]
+        return []
+
+    def _record(self, batch: dict, preds) -> dict:
         out = {"preds": preds, "target": batch["transcript"], "speaker": batch.get("speaker")}
         if batch.get("keywords") is not None:
             out["keywords"] = batch["keywords"]
@@ -427,6 +459,26 @@ class CBWhisper:
             self.test_step_outputs = []
         self.test_step_outputs.append(out)
         return out
+
+    def test_step(self, batch: dict, batch_idx: int = 0, rng: Optional[random.Random] = None):
+        """cb_whisper.py:218-242: the oracle keyword list, then forward."""
+        oracle = self._batch_oracle(batch, rng)
+        preds = self.forward(input_features=batch["utterance"]["features"],
+                             attention_mask=batch["utterance"].get("attention_mask"), oracle=oracle)
+        return self._record(batch, preds)
+
+    def test_step_batch(self, batches: Sequence[dict], rng: Optional[random.Random] = None) -> List[dict]:
+        """test_step over several one-clip batches (each of <= 30 s, all of one length) in one transcribe_batch call:
+        appends what the test_step calls would append, in order, and draws from ``rng`` as they would in sequence."""
+        batches = list(batches)
+        if not batches:
+            return []
+        oracles = [self._batch_oracle(b, rng) for b in batches]
+        feats = torch.cat([b["utterance"]["features"] for b in batches], 0)
+        if feats.size(0) != len(batches):
+            raise ValueError("test_step_batch takes batches of one clip each")
+        preds = self.transcribe_batch(feats, oracles)
+        return [self._record(b, p) for b, p in zip(batches, preds)]
 
     def on_test_epoch_end(self, num_bootstraps: int = 1000, alpha: float = 5) -> Dict[str, float]:
         """cb_whisper.py:244-289: entity recall (scorer.entity_recall, ner_tags='ALL',

@@ -432,6 +432,61 @@ class PBAWhisper:
         finally:
             self._controls = {}
 
+    def generate_batch(self, input_features: torch.Tensor, task: Optional[str] = None, language: Optional[str] = None,
+                       return_timestamps: Optional[bool] = None, num_beams: int = 1,
+                       max_new_tokens: Optional[int] = None, length_penalty: float = 1.0,
+                       keyword_spotting: Optional[Callable] = None) -> List[torch.Tensor]:
+        """A batch of short clips in one call: input_features [N, n_mel, T <= 3000] -> N LongTensors [1, n_i], element
+        i equal to ``generate(input_features[i:i + 1], ...)`` with the same arguments (the reference, and generate,
+        take one clip of 30 s or less at a time, pba_whisper.py:283-338).  One ``keyword_spotting`` call over all
+        clips (each clip its own prompt), per-clip ``shortform_prefix``, then every clip's greedy or beam search in
+        lock step on one decoder state of up to 80 rows (DecoderEngine.greedy_windows / beam_search_windows with
+        ``max_rows=80``: each row's logits are those of the clip decoded alone, so are the tokens; CBW_DEC_WIDE=0
+        keeps 16 rows, with the same results).  The clips are encoded one by one: the encoder picks its GEMM tiling
+        and K-split by the rows of a call, so a batched call would not give a clip the bits of its own call.
+        The controls go down as arguments (nothing is left in ``_controls``).  Refused before any GPU work: T > 3000
+        (ValueError: long-form is generate's), ``language=None`` on a multilingual checkpoint (NotImplementedError:
+        the free language position runs on the host search), more than 16 beams, and a forced prefix of a single
+        token (both NotImplementedError: generate decodes those on the host loop).  Sampling and the temperature
+        fallback are generate's."""
+        if input_features is None or input_features.dim() != 3:
+            raise ValueError("PBAWhisper.generate_batch needs input_features [N, n_mel, T]")
+        N, _, T = input_features.shape
+        if T > N_FRAMES:
+            raise ValueError("PBAWhisper.generate_batch takes clips of at most 3000 mel frames (30 seconds); long-form "
+                             "audio goes through generate")
+        if language is None and not self.tokens.english_only:
+            raise NotImplementedError("PBAWhisper.generate_batch: language=None on a multilingual checkpoint (the free "
+                                      "language position) is not restated for batches; pass a language")
+        if not 1 <= int(num_beams) <= 16:
+            raise NotImplementedError("PBAWhisper.generate_batch: num_beams must be in [1, 16]")
+        ts = bool(return_timestamps)
+        init = self.tokens.init_tokens(language, task, ts)
+        if len(init) < 2:
+            raise NotImplementedError("PBAWhisper.generate_batch: a forced prefix of one token is decoded on the host "
+                                      "loop; use generate")
+        if N == 0:
+            return []
+        spot = keyword_spotting or (lambda input_features, start_of_prev=False: [[] for _ in range(input_features.size(0))])
+        prompts = [list(p) for p in spot(input_features=input_features, start_of_prev=True)]
+        if len(prompts) != N:
+            raise ValueError(f"keyword_spotting returned {len(prompts)} prompts for {N} clips")
+        prefixes = [shortform_prefix(p, init, self.max_length) for p in prompts]
+        feats = torch.nn.functional.pad(input_features, (0, N_FRAMES - T)) if T < N_FRAMES else input_features
+        windows = [(self.encode(self._pack(feats[i:i + 1]))[0], prefixes[i]) for i in range(N)]
+        limits = [self.max_length if max_new_tokens is None else min(self.max_length, len(p) + max_new_tokens)
+                  for p in prefixes]
+        bias, bias_begin = self._biases()
+        rules = self.rules if ts else None
+        if num_beams <= 1:
+            seqs = self.decoder.greedy_windows(windows, self.tokens.eot, limits, bias, bias_begin, rules, max_rows=80)
+        else:
+            begins = [len(p) for p in prefixes]
+            bias_ats = [(lambda pos, b=b: bias_begin if pos == b else bias) for b in begins]
+            seqs = self.decoder.beam_search_windows(windows, num_beams, self.tokens.eot, limits, bias_ats, rules, begins,
+                                                    1, length_penalty=length_penalty, max_rows=80)
+        return [torch.tensor([list(q)[len(p):]], dtype=torch.long) for q, p in zip(seqs, prompts)]
+
     # a caller's transformers generation controls this build restates (VERDICT r05 item 8; the reference forwards
     # **kwargs into GenerationMixin.generate, pba_whisper.py:320-331), pinned by tests/golden/gen_controls_micro.npz
     _CONTROLS = ("length_penalty", "num_return_sequences", "max_length", "repetition_penalty", "no_repeat_ngram_size")
@@ -651,11 +706,12 @@ class PBAWhisper:
                 return self.decoder.beam_search_windows([(enc[i], prefixes[i]) for i in range(len(segs))], num_beams,
                                                         self.tokens.eot, max_length, bias_at,
                                                         self.rules if timestamps else None, begin, begin,
-                                                        length_penalty=self._controls.get("length_penalty", 1.0))
+                                                        length_penalty=self._controls.get("length_penalty", 1.0),
+                                                        max_rows=80)   # 16 under CBW_DEC_WIDE=0 (cbw.decoder.row_cap)
             if num_beams <= 1 and len(segs) > 1 and all(len(p) >= 2 for p in prefixes) and _dev_greedy():
                 return self.decoder.greedy_windows([(enc[i], prefixes[i]) for i in range(len(segs))], self.tokens.eot,
                                                    [self._window_max_length(len(p), max_new_tokens) for p in prefixes],
-                                                   bias, bias_begin, self.rules if timestamps else None)
+                                                   bias, bias_begin, self.rules if timestamps else None, max_rows=80)
             return [self.decode_window(enc[i:i + 1], prefixes[i], num_beams, max_new_tokens, timestamps=timestamps,
                                        decoder_prompt_len=begin) for i in range(len(segs))]
 

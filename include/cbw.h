@@ -419,6 +419,15 @@ int cbw_decoder_prefill_rows(cbw_decoder* h, const int32_t* tokens, int T, int s
                              void* state, int64_t state_bytes, float* logits, cbw_stream_t stream);
 int cbw_decoder_step_rows(cbw_decoder* h, const int32_t* tokens, const int32_t* pos_rows, int B, int Benc, void* state,
                           int64_t state_bytes, float* logits, cbw_stream_t stream);
+/* cbw_decoder_step_rows for 1 <= B <= CBW_DEC_WIDE_ROWS rows (a batch of short clips: 16 windows x 5 beams in one
+ * step): every Linear runs as ceil(B / 16) row groups in one launch, each group on the 16-row kernel of
+ * cbw_decoder_step_rows, and the embedding and attention launches are those of the narrower step -- so each row's
+ * logits equal, bit for bit, those of a step over its window alone on a state of <= 16 rows.  B % Benc == 0 and
+ * B / Benc <= 8 (the split cross-attention reads a window's K/V once for its rows).  Each row group re-reads the
+ * Linear's weights.  cbw_decoder_prefill_rows and cbw_decoder_reorder serve a state of up to 80 rows as they are. */
+#define CBW_DEC_WIDE_ROWS 80
+int cbw_decoder_step_wide(cbw_decoder* h, const int32_t* tokens, const int32_t* pos_rows, int B, int Benc, void* state,
+                          int64_t state_bytes, float* logits, cbw_stream_t stream);
 /* Cross-attention probabilities for token-level timestamps (transformers WhisperGenerationMixin.
  * _extract_token_timestamps, reached from pba_whisper.py:333-336 and the long-form return_token_timestamps path,
  * :425-442): the decoder runs teacher-forced over tokens[0..T) (device int32) against encoder slot 0 of `state`
@@ -581,6 +590,16 @@ int cbw_linear_rows(const uint16_t* x, const float* xf, int ldx, const float* ln
                     int K, int flags, uint16_t* kv_k, uint16_t* kv_v, int64_t kv_ld, int kv_D, const int32_t* kv_pos,
                     int kv_pos_rows, cbw_stream_t stream);
 const char* cbw_linear_rows_kernel(int M, int N, int K, int ln);
+/* cbw_linear_rows over 1 <= M <= CBW_DEC_WIDE_ROWS rows, as cbw_decoder_step_wide launches it: ceil(M / 16) row groups
+ * in one launch (a second grid coordinate), group g = the 16-row kernel of the shape's family on rows [16 g, 16 g + 16)
+ * with x / xf, res, y, kv_k / kv_v and kv_pos moved by the group's rows.  Row m carries the bits cbw_linear_rows gives
+ * it in a call over its 16-row slice.  CBW_GEMV_WIDE_ORDER=groups (read per call) makes the groups the fast grid
+ * coordinate instead of the column blocks.  cbw_linear_rows_wide_kernel: the kernel's name, "" for a rejected shape. */
+int cbw_linear_rows_wide(const uint16_t* x, const float* xf, int ldx, const float* ln_g, const float* ln_b, float ln_eps,
+                         const uint16_t* w, const float* bias, const void* res, int res_ld, void* y, int ldy, int M,
+                         int N, int K, int flags, uint16_t* kv_k, uint16_t* kv_v, int64_t kv_ld, int kv_D,
+                         const int32_t* kv_pos, int kv_pos_rows, cbw_stream_t stream);
+const char* cbw_linear_rows_wide_kernel(int M, int N, int K, int ln);
 /* The decoder's (and encoder's) LayerNorm launch (building block for the tests): x f32 [rows][D] -> y bf16 [rows][D]
  * and / or y32 f32 [rows][D] (either may be NULL, not both) = (x - mean) * rsqrt(var + eps) * g + b, one wave per row,
  * fp32; D % 4 == 0, operands 16-byte aligned; asynchronous. */
