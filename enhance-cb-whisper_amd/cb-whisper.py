@@ -10,8 +10,9 @@ builds the same CBWhisper -- checkpoints are local HF-format directories (cbw.ch
 audio + transcript loaders (data/dataset.py) are dataset I/O, out of scope: ``--synthetic N`` runs N seeded
 30 s clips through ``test_step`` / ``on_test_epoch_end`` (mel -> spotting -> prompt -> beam search on the
 GPU) so the YAML -> model -> GPU path runs end to end (``--batch N``: in groups of N through ``test_step_batch``,
-the clips of a group decoded in lock step; 1, the default, is the clip-by-clip path); without it the runner builds
-the model and reports it.  ``fit``/``validate`` are training and out of scope.
+the clips of a group decoded in lock step; 1, the default, is the clip-by-clip path; ``--token-timestamps`` with
+``--batch N`` adds each clip's (token, time in seconds) pairs from ``transcribe_batch``); without it the runner
+builds the model and reports it.  ``fit``/``validate`` are training and out of scope.
 """
 from __future__ import annotations
 
@@ -30,7 +31,8 @@ if HERE not in sys.path:
 def main(argv=None):
     from cbw import cli
     argv = list(sys.argv[1:] if argv is None else argv)
-    own, overrides = cli.split_argv(argv, ("--config", "--synthetic", "--seed", "--max-new-tokens", "--batch"))
+    own, overrides = cli.split_argv(argv, ("--config", "--synthetic", "--seed", "--max-new-tokens", "--batch",
+                                           "--token-timestamps!"))
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("subcommand", choices=["test", "fit", "validate"])
     ap.add_argument("--config", required=True)
@@ -38,9 +40,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-new-tokens", type=int, default=None)
     ap.add_argument("--batch", type=int, default=1, help="synthetic clips per test_step_batch call (1: test_step)")
+    ap.add_argument("--token-timestamps", action="store_true",
+                    help="with --batch N: print each clip's (token, time) pairs (transcribe_batch)")
     sub = [a for a in overrides if not a.startswith("--")][:1]
     args = ap.parse_args(sub + own)
     overrides = [a for a in overrides if a not in sub]
+    if args.token_timestamps and args.batch <= 1:
+        raise SystemExit("--token-timestamps needs --batch N with N > 1 (generate gives a short clip none)")
     if args.subcommand != "test":
         raise SystemExit(f"'{args.subcommand}' is training and out of scope for the MI355X inference path")
     cfg = cli.load_config(args.config, overrides)
@@ -81,6 +87,10 @@ def main(argv=None):
         spotted = model.last_spotted or []
         for j, (i, r) in enumerate(zip(ids, rs)):
             out.append({"clip": i, "spotted": spotted[j] if j < len(spotted) else [], "pred": r["preds"]})
+        if args.token_timestamps:   # a second pass over the group, for the times alone
+            feats = torch.cat([batch_of(i)["utterance"]["features"] for i in ids], 0)
+            for o, r in zip(out[-len(ids):], model.transcribe_batch(feats, return_token_timestamps=True)):
+                o["token_timestamps"] = [[t, round(s, 2)] for t, s in zip(r["tokens"], r["token_timestamps"])]
     print(json.dumps({"results": out}))
     return 0
 

@@ -32,6 +32,15 @@ class DecoderConfig(ctypes.Structure):
                 ("max_len", c_int)]
 
 
+class TokenTsWindow(ctypes.Structure):
+    """cbw_token_ts_window (cbw.h): one window of cbw_align_matrix_batch / cbw_dtw_dev_batch."""
+    _fields_ = [("T_all", ctypes.c_int32), ("t0", ctypes.c_int32), ("T", ctypes.c_int32), ("F", ctypes.c_int32),
+                ("probs_off", c_int64), ("matrix_off", c_int64), ("ws_off", c_int64)]
+
+
+TOKEN_TS_MAX_WINDOWS = 16   # CBW_TOKEN_TS_MAX_WINDOWS
+
+
 # name: (restype, argtypes) — mirrors include/cbw.h exactly (tests check every symbol is exported)
 SIGNATURES = {
     "cbw_version": (c_int, []),
@@ -154,6 +163,12 @@ SIGNATURES = {
                                  c_int64, c_void_p]),
     "cbw_dtw_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                             c_void_p]),
+    "cbw_decoder_cross_attn_probs_slot": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                  c_void_p, c_int64, c_void_p, c_void_p]),
+    "cbw_token_ts_ws_bytes_batch": (c_int64, [c_void_p, c_int]),
+    "cbw_align_matrix_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_void_p]),
+    "cbw_dtw_dev_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "cbw_logprob_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cbw_timestamp_rules": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p]),

@@ -191,6 +191,38 @@ class DecoderEngine:
                        "cbw_decoder_cross_attn_probs")
         return probs
 
+    def cross_attn_probs_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]],
+                                 heads: np.ndarray) -> List[torch.Tensor]:
+        """``cross_attn_probs`` for several windows, windows = [(enc_out [1500, D], row tokens)]: one device tensor
+        f32 [n, len(tokens_i), 1500] per window, views of one buffer.  Groups of at most 16 windows share a lock-step
+        state of one row per window (start_windows(g, 1): whatever state the engine held is gone): window w of a group
+        is encoder slot w and cache row w, set_window then one cbw_decoder_cross_attn_probs_slot call -- the windows'
+        rows are not joined into one pass, whose GEMM tiling would follow the row count, so each window's
+        probabilities are those of start() + cross_attn_probs() on it alone, bit for bit.  No host synchronisation."""
+        n = heads.size // 2
+        lens = [len(t) for _, t in windows]
+        if min(lens, default=1) < 1:
+            raise ValueError("cross_attn_probs_windows: an empty row")
+        toks = torch.as_tensor([int(t) for _, row in windows for t in row], dtype=torch.int32).to(self.device)
+        probs = torch.empty(n * 1500 * sum(lens), dtype=torch.float32, device=self.device)
+        out, at = [], 0
+        with torch.cuda.device(self.device):
+            for g0 in range(0, len(windows), 16):
+                group = windows[g0:g0 + 16]
+                self.start_windows(len(group), 1)
+                rows, slots = self._shape
+                for slot, (enc_out, row) in enumerate(group):
+                    T = len(row)
+                    view = probs[n * 1500 * at:n * 1500 * (at + T)].view(n, T, 1500)
+                    self.set_window(slot, enc_out)
+                    _lib.check(self.lib.cbw_decoder_cross_attn_probs_slot(
+                        self.h, toks.data_ptr() + 4 * at, T, heads.ctypes.data, n, slot, slot, rows, slots,
+                        self._state.data_ptr(), self._state.numel(), view.data_ptr(), _lib.stream_handle()),
+                        "cbw_decoder_cross_attn_probs_slot")
+                    out.append(view)
+                    at += T
+        return out
+
     def reorder(self, src_rows: Sequence[int], length: int):
         rows, Benc = self._shape
         self._rows.copy_(torch.as_tensor(list(src_rows), dtype=torch.int32))

@@ -295,6 +295,22 @@ hipError_t cbw_align_matrix_launch(const float* probs, int n, int T_all, int t0,
                                    float* matrix, int* degenerate, hipStream_t st);
 hipError_t cbw_dtw_launch(const float* matrix, int T, int F, int* first_frame, int* text_idx, int* time_idx, int* len,
                           uint32_t* trace, hipStream_t st);
+// the same two for N <= CBW_TS_MAX_WINDOWS windows in one launch each: the windows' table goes to the kernel by value
+// (no upload); window i's arithmetic is that of the single-window launch.  degenerate int32 [N] (zeroed by the
+// caller), first_frame int32 [N][ld], ld >= the largest T; no path.
+constexpr int CBW_TS_MAX_WINDOWS = 16;   // CBW_TOKEN_TS_MAX_WINDOWS (cbw.h)
+struct cbw_ts_win {
+    const float* probs;   // [n][T_all][1500]
+    float* matrix;        // [T][F]
+    uint32_t* trace;      // cbw_dtw_trace_words(T, F) words
+    int T_all, t0, T, F;
+};
+struct cbw_ts_batch {
+    cbw_ts_win w[CBW_TS_MAX_WINDOWS];
+};
+hipError_t cbw_align_matrix_batch_launch(const cbw_ts_batch& b, int N, int n, int width, int* degenerate,
+                                         hipStream_t st);
+hipError_t cbw_dtw_batch_launch(const cbw_ts_batch& b, int N, int* first_frame, int ld, hipStream_t st);
 hipError_t cbw_dec_reorder_kv(uint16_t* ks, uint16_t* vs, const int* rows, int B, int n_layers, int64_t layer_elems,
                               int64_t row_elems, int64_t copy_elems, hipStream_t st);
 // decode-step self-attention in one launch: row r (its own K/V batch r) over min(n_keys, n_keys_pos[nk_rows ? r : 0]

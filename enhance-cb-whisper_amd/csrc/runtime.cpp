@@ -3171,19 +3171,41 @@ int cbw_decoder_prefill_rows(cbw_decoder* h, const int32_t* tokens, int T, int s
     return last.ln_lin(s.ph + (size_t)(T - 1) * h->cfg.d_model, h->lnf, h->emb, logits, CBW_EPI_OUT_F32);
 }
 
-int cbw_decoder_cross_attn_probs(cbw_decoder* h, const int32_t* tokens, int T, const int32_t* heads, int n, int B,
-                                 int Benc, void* state, int64_t state_bytes, float* probs, cbw_stream_t stream) {
+}  // extern "C"
+namespace {
+// cbw_decoder_cross_attn_probs and its slot-taking form: the checks, then the probed prefill of slot `slot`, row r0
+int dec_cross_attn_probs(const std::string& who, cbw_decoder* h, const int32_t* tokens, int T, const int32_t* heads,
+                         int n, int slot, int r0, int B, int Benc, void* state, int64_t state_bytes, float* probs,
+                         cbw_stream_t stream) {
     CHK(dec_check(h, tokens && heads && state && probs, B, Benc));
-    if (T < 1 || T > h->cfg.max_len || n < 1)
-        return fail(CBW_ERR_INVALID, "cross_attn_probs needs 1 <= T <= max_len, n >= 1");
-    if (h->cfg.d_model != 64 * h->cfg.n_heads) return fail(CBW_ERR_INVALID, "cross_attn_probs: head dim must be 64");
+    if (T < 1 || T > h->cfg.max_len || n < 1) return fail(CBW_ERR_INVALID, who + " needs 1 <= T <= max_len, n >= 1");
+    if (h->cfg.d_model != 64 * h->cfg.n_heads) return fail(CBW_ERR_INVALID, who + ": head dim must be 64");
     for (int i = 0; i < n; ++i)
         if (heads[2 * i] < 0 || heads[2 * i] >= h->cfg.n_layers || heads[2 * i + 1] < 0 ||
             heads[2 * i + 1] >= h->cfg.n_heads)
-            return fail(CBW_ERR_INVALID, "cross_attn_probs: (layer, head) out of range");
+            return fail(CBW_ERR_INVALID, who + ": (layer, head) out of range");
+    if (slot < 0 || slot >= Benc || r0 < 0 || r0 >= B)
+        return fail(CBW_ERR_INVALID, who + " needs 0 <= slot < Benc, 0 <= r0 < B");
     DecState s;
     CHK(dec_state(h, state, state_bytes, B, Benc, &s));
-    return dec_prefill_layers(h, tokens, T, 0, 0, 1, B, Benc, s, (hipStream_t)stream, heads, n, probs);
+    return dec_prefill_layers(h, tokens, T, slot, r0, 1, B, Benc, s, (hipStream_t)stream, heads, n, probs);
+}
+}  // namespace
+extern "C" {
+
+int cbw_decoder_cross_attn_probs(cbw_decoder* h, const int32_t* tokens, int T, const int32_t* heads, int n, int B,
+                                 int Benc, void* state, int64_t state_bytes, float* probs, cbw_stream_t stream) {
+    return dec_cross_attn_probs("cross_attn_probs", h, tokens, T, heads, n, 0, 0, B, Benc, state, state_bytes, probs,
+                                stream);
+}
+
+int cbw_decoder_cross_attn_probs_slot(cbw_decoder* h, const int32_t* tokens, int T, const int32_t* heads, int n,
+                                      int slot, int r0, int B, int Benc, void* state, int64_t state_bytes,
+                                      float* probs, cbw_stream_t stream) {
+    if (!h || !tokens || !heads || !state || !probs)
+        return fail(CBW_ERR_INVALID, "cbw_decoder_cross_attn_probs_slot: null argument");
+    return dec_cross_attn_probs("cbw_decoder_cross_attn_probs_slot", h, tokens, T, heads, n, slot, r0, B, Benc, state,
+                                state_bytes, probs, stream);
 }
 
 int cbw_dtw(const double* matrix, int rows, int cols, int32_t* text_idx, int32_t* time_idx, int* len) {
@@ -3263,6 +3285,68 @@ int cbw_dtw_dev(const float* matrix, int T, int F, int32_t* first_frame, int32_t
     if (F < 1 || F > CBW_DTW_MAX_F) return fail(CBW_ERR_INVALID, "cbw_dtw_dev needs 1 <= F <= 1500");
     CHK(token_ts_ws_check("cbw_dtw_dev", T, F, ws, ws_bytes));
     HIPCHK(cbw_dtw_launch(matrix, T, F, first_frame, text_idx, time_idx, len, (uint32_t*)ws, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+}  // extern "C"
+namespace {
+// the checks of the batched entries, per window, and the table the kernels take: base pointers plus offsets
+int token_ts_batch(const std::string& who, const cbw_token_ts_window* win, int N, int min_T, const float* probs,
+                   float* matrix, void* ws, int64_t ws_bytes, cbw_ts_batch* out) {
+    if (!win) return fail(CBW_ERR_INVALID, who + ": null win");
+    if (N < 1 || N > CBW_TOKEN_TS_MAX_WINDOWS) return fail(CBW_ERR_INVALID, who + " needs 1 <= N <= 16 windows");
+    if (ws_bytes >= 0 && (!ws || ((uintptr_t)ws & 3))) return fail(CBW_ERR_INVALID, who + ": ws null or misaligned");
+    for (int i = 0; i < N; ++i) {
+        const cbw_token_ts_window& w = win[i];
+        const std::string at = who + ": window " + std::to_string(i);
+        if (w.T < min_T || w.T > 1024) return fail(CBW_ERR_INVALID, at + " needs " + std::to_string(min_T) + " <= T <= 1024");
+        if (w.t0 < 0 || w.T_all < w.T || w.t0 > w.T_all - w.T)
+            return fail(CBW_ERR_INVALID, at + ": [t0, t0 + T) outside [0, T_all)");
+        if (w.F < 1 || w.F > CBW_DTW_MAX_F) return fail(CBW_ERR_INVALID, at + " needs 1 <= F <= 1500");
+        if (w.probs_off < 0 || w.matrix_off < 0 || w.ws_off < 0 || (w.ws_off & 3))
+            return fail(CBW_ERR_INVALID, at + ": an offset is negative, or ws_off no multiple of 4");
+        const int64_t need = cbw_dtw_trace_words(w.T, w.F) * (int64_t)sizeof(uint32_t);
+        if (ws_bytes >= 0 && (need > ws_bytes || w.ws_off > ws_bytes - need))
+            return fail(CBW_ERR_INVALID, at + ": ws smaller than ws_off + cbw_token_ts_ws_bytes");
+        if (out) out->w[i] = {probs + w.probs_off, matrix + w.matrix_off, (uint32_t*)((char*)ws + w.ws_off), w.T_all,
+                              w.t0, w.T, w.F};
+    }
+    return CBW_OK;
+}
+}  // namespace
+extern "C" {
+
+int64_t cbw_token_ts_ws_bytes_batch(const cbw_token_ts_window* win, int N) {
+    CHK(token_ts_batch("cbw_token_ts_ws_bytes_batch", win, N, 1, nullptr, nullptr, nullptr, -1, nullptr));
+    int64_t sum = 0;
+    for (int i = 0; i < N; ++i) sum += cbw_dtw_trace_words(win[i].T, win[i].F) * (int64_t)sizeof(uint32_t);
+    return sum;
+}
+
+int cbw_align_matrix_batch(const float* probs, int n, const cbw_token_ts_window* win, int N, int width, float* matrix,
+                           int32_t* degenerate, void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    const char* who = "cbw_align_matrix_batch";
+    if (!probs || !matrix || !degenerate) return fail(CBW_ERR_INVALID, std::string(who) + ": null probs, matrix or degenerate");
+    if (n < 1) return fail(CBW_ERR_INVALID, std::string(who) + ": n < 1");
+    if (width < 1 || width > 7 || !(width & 1)) return fail(CBW_ERR_INVALID, std::string(who) + ": width must be 1, 3, 5 or 7");
+    cbw_ts_batch b{};
+    CHK(token_ts_batch(who, win, N, 2, probs, matrix, ws, ws_bytes < 0 ? 0 : ws_bytes, &b));
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(degenerate, 0, N * sizeof(int32_t), st));
+    HIPCHK(cbw_align_matrix_batch_launch(b, N, n, width, degenerate, st));
+    return CBW_OK;
+}
+
+int cbw_dtw_dev_batch(const float* matrix, const cbw_token_ts_window* win, int N, int32_t* first_frame, int ld,
+                      void* ws, int64_t ws_bytes, cbw_stream_t stream) {
+    const char* who = "cbw_dtw_dev_batch";
+    if (!matrix || !first_frame) return fail(CBW_ERR_INVALID, std::string(who) + ": null matrix or first_frame");
+    cbw_ts_batch b{};
+    // the matrices are read here; the table's probs entries are not used by the DTW
+    CHK(token_ts_batch(who, win, N, 1, nullptr, const_cast<float*>(matrix), ws, ws_bytes < 0 ? 0 : ws_bytes, &b));
+    for (int i = 0; i < N; ++i)
+        if (ld < win[i].T) return fail(CBW_ERR_INVALID, std::string(who) + ": ld below the largest T");
+    HIPCHK(cbw_dtw_batch_launch(b, N, first_frame, ld, (hipStream_t)stream));
     return CBW_OK;
 }
 

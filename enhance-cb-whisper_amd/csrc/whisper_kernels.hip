@@ -5,6 +5,7 @@
 // src/data/dataset.py:332-339) and HF WhisperEncoder (called at
 // src/model/cb_whisper.py:100-104, src/utils.py:188-192); see oracle/mel.py and
 // oracle/encoder.py for the restated algorithms these kernels are checked against.
+#include <algorithm>
 #include <cfloat>
 
 #include "cbw_common.h"
@@ -490,14 +491,14 @@ __device__ __forceinline__ float median_of(float (&v)[W]) {
     return v[W / 2];
 }
 
+// the block of frame tile `tile` of one window (the kernels below: one window, or a batch with the window as grid.y)
 template <int W>
-__global__ __launch_bounds__(32 * AM_G) void align_matrix_kernel(const float* __restrict__ probs, int n, int T_all,
-                                                                 int t0, int T, int F, float* __restrict__ matrix,
-                                                                 int* __restrict__ degenerate) {
+__device__ __forceinline__ void align_matrix_tile(const float* __restrict__ probs, int n, int T_all, int t0, int T,
+                                                  int F, float* __restrict__ matrix, int* __restrict__ degenerate,
+                                                  int tile, double (&part)[AM_G][33]) {
     constexpr int P = W / 2, FT = 32 - 2 * P;
-    __shared__ double part[AM_G][33];
     const int lane = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int c = blockIdx.x * FT - P + lane;   // the lane's column before the reflection
+    const int c = tile * FT - P + lane;   // the lane's column before the reflection
     int fr = c < 0 ? -c : c;
     if (fr >= F) fr = 2 * (F - 1) - fr;
     fr = min(max(fr, 0), F - 1);                // lanes behind the last halo: some frame, never stored
@@ -539,6 +540,32 @@ __global__ __launch_bounds__(32 * AM_G) void align_matrix_kernel(const float* __
                 *o = acc;
             }
         }
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(32 * AM_G) void align_matrix_kernel(const float* __restrict__ probs, int n, int T_all,
+                                                                 int t0, int T, int F, float* __restrict__ matrix,
+                                                                 int* __restrict__ degenerate) {
+    __shared__ double part[AM_G][33];
+    align_matrix_tile<W>(probs, n, T_all, t0, T, F, matrix, degenerate, blockIdx.x, part);
+}
+
+// N windows in one launch: grid = (the frame tiles of the window with the most, N), the table by value in the kernel
+// arguments.  A block beyond its window's tiles leaves before any barrier; a window too short to filter (F <= W / 2)
+// takes the W = 1 tile, as cbw_align_matrix_launch chooses for it.  degenerate: one flag per window.
+template <int W>
+__global__ __launch_bounds__(32 * AM_G) void align_matrix_batch_kernel(const cbw_ts_batch b, int n,
+                                                                       int* __restrict__ degenerate) {
+    __shared__ double part[AM_G][33];
+    const cbw_ts_win& w = b.w[blockIdx.y];
+    const int tile = blockIdx.x;
+    if (W > 1 && w.F <= W / 2) {
+        if (tile * 32 >= w.F) return;
+        align_matrix_tile<1>(w.probs, n, w.T_all, w.t0, w.T, w.F, w.matrix, degenerate + blockIdx.y, tile, part);
+    } else {
+        if (tile * (32 - 2 * (W / 2)) >= w.F) return;
+        align_matrix_tile<W>(w.probs, n, w.T_all, w.t0, w.T, w.F, w.matrix, degenerate + blockIdx.y, tile, part);
     }
 }
 
@@ -590,65 +617,13 @@ __device__ __forceinline__ uint32_t dtw_block16(const float (&mv)[16], int b, in
     return word;
 }
 
-__global__ __launch_bounds__(DTW_MAX_T) void dtw_kernel(const float* __restrict__ m, int T, int F,
-                                                        int* __restrict__ first_frame, int* __restrict__ text_idx,
-                                                        int* __restrict__ time_idx, int* __restrict__ len,
-                                                        uint32_t* __restrict__ trace) {
-    __shared__ float sh[2][DTW_MAX_T];
-    __shared__ int n_sh;
-    const int i = threadIdx.x;
-    const bool row = i < T;
-    const float* __restrict__ mr = m + (int64_t)min(i, T - 1) * F;
-    const int nblk = (T + F - 1 + 15) >> 4;
-    float ma[16], mb[16];   // two blocks of matrix entries, used in turn: no copy between them
-    dtw_load16(mr, -i, F, ma);
-    float left = INFINITY, diag = i == 0 ? 0.f : INFINITY;
-    for (int b = 0; b < nblk; b += 2) {
-        dtw_load16(mr, 16 * (b + 1) - i, F, mb);
-        const uint32_t wa = dtw_block16(ma, b, i, row, F, sh, left, diag);
-        if (row) trace[(int64_t)b * T + i] = wa;
-        if (b + 1 == nblk) break;
-        dtw_load16(mr, 16 * (b + 2) - i, F, ma);
-        const uint32_t wb = dtw_block16(mb, b + 1, i, row, F, sh, left, diag);
-        if (row) trace[(int64_t)(b + 1) * T + i] = wb;
-    }
-    __syncthreads();   // the trace words of every wave are in memory
-    if (i == 0) {
-        int r = T, c = F, n = 0;   // 1-based, as cbw_dtw's tables: row 0 walks left, column 0 walks up
-        int64_t at = -1;
-        uint32_t word = 0;
-        while (r > 0 || c > 0) {
-            if (text_idx) {
-                text_idx[n] = r - 1;
-                time_idx[n] = c - 1;
-            }
-            ++n;
-            uint32_t t;
-            if (c == 0) t = 1;
-            else if (r == 0) t = 2;
-            else {
-                const int d = r + c - 2;
-                const int64_t idx = (int64_t)(d >> 4) * T + (r - 1);
-                if (idx != at) word = trace[idx], at = idx;
-                t = (word >> (2 * (d & 15))) & 3u;
-            }
-            if (t != 2) first_frame[r - 1] = c - 1, --r;
-            if (t != 1) --c;
-        }
-        n_sh = n;
-        if (len) *len = n;
-    }
-    __syncthreads();
-    if (text_idx) {
-        const int n = n_sh;
-        for (int k = i; k < n / 2; k += blockDim.x) {
-            const int a = text_idx[k], b = text_idx[n - 1 - k];
-            text_idx[k] = b, text_idx[n - 1 - k] = a;
-            const int p = time_idx[k], q = time_idx[n - 1 - k];
-            time_idx[k] = q, time_idx[n - 1 - k] = p;
-        }
-    }
-}
+// the kernel: once for one window, once with the window as the grid's coordinate
+#define DTW_BATCH 0
+#include "dtw_kernel.inc"
+#undef DTW_BATCH
+#define DTW_BATCH 1
+#include "dtw_kernel.inc"
+#undef DTW_BATCH
 
 // Split-key decode attention (flash-decoding): workgroup = (key chunk of DS_CHUNK keys, head, kv batch)
 // serving ALL the R query rows that share the kv batch (the beams of a window against its cross K/V: K/V
@@ -1016,6 +991,39 @@ hipError_t cbw_dtw_launch(const float* matrix, int T, int F, int* first_frame, i
     // the x dimension of the grid stays free for a batch of matrices
     hipLaunchKernelGGL(dtw_kernel, dim3(1), dim3((T + 63) / 64 * 64), 0, st, matrix, T, F, first_frame, text_idx,
                        time_idx, len, trace);
+    return hipGetLastError();
+}
+
+hipError_t cbw_align_matrix_batch_launch(const cbw_ts_batch& b, int N, int n, int width, int* degenerate,
+                                         hipStream_t st) {
+    if (N < 1 || N > CBW_TS_MAX_WINDOWS || n < 1 || width < 1 || width > 7 || !(width & 1)) return hipErrorInvalidValue;
+    int tiles = 0;
+    for (int i = 0; i < N; ++i) {
+        const cbw_ts_win& w = b.w[i];
+        if (w.T < 1 || w.t0 < 0 || w.t0 + w.T > w.T_all || w.F < 1 || w.F > 1500) return hipErrorInvalidValue;
+        const int tile = 32 - 2 * (w.F <= width / 2 ? 0 : width / 2);
+        tiles = std::max(tiles, (w.F + tile - 1) / tile);
+    }
+    const dim3 grid(tiles, N), block(32 * AM_G);
+    switch (width) {
+    case 1: hipLaunchKernelGGL(align_matrix_batch_kernel<1>, grid, block, 0, st, b, n, degenerate); break;
+    case 3: hipLaunchKernelGGL(align_matrix_batch_kernel<3>, grid, block, 0, st, b, n, degenerate); break;
+    case 5: hipLaunchKernelGGL(align_matrix_batch_kernel<5>, grid, block, 0, st, b, n, degenerate); break;
+    default: hipLaunchKernelGGL(align_matrix_batch_kernel<7>, grid, block, 0, st, b, n, degenerate);
+    }
+    return hipGetLastError();
+}
+
+hipError_t cbw_dtw_batch_launch(const cbw_ts_batch& b, int N, int* first_frame, int ld, hipStream_t st) {
+    if (N < 1 || N > CBW_TS_MAX_WINDOWS) return hipErrorInvalidValue;
+    int Tmax = 0;
+    for (int i = 0; i < N; ++i) {
+        const cbw_ts_win& w = b.w[i];
+        if (w.T < 1 || w.T > DTW_MAX_T || w.F < 1 || w.F > CBW_DTW_MAX_F) return hipErrorInvalidValue;
+        Tmax = std::max(Tmax, w.T);
+    }
+    if (ld < Tmax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dtw_batch_kernel, dim3(N), dim3((Tmax + 63) / 64 * 64), 0, st, b, first_frame, ld);
     return hipGetLastError();
 }
 

@@ -422,18 +422,25 @@ class CBWhisper:
         special = set(range(self.whisper.tokens.eot, self.whisper.decoder_config[0]))
         return self.detokenize([t for t in toks if t not in special]).strip()
 
-    def transcribe_batch(self, input_features: torch.Tensor, oracles: Optional[Sequence[Sequence[str]]] = None) -> List:
+    def transcribe_batch(self, input_features: torch.Tensor, oracles: Optional[Sequence[Sequence[str]]] = None,
+                         return_token_timestamps: bool = False) -> List:
         """A batch of short clips [N, n_mel, T <= 3000] in one call (PBAWhisper.generate_batch): element i equals
-        ``forward(input_features[i:i + 1], oracle=oracles[i])``.  Every clip gets its own keywords."""
+        ``forward(input_features[i:i + 1], oracle=oracles[i])``.  Every clip gets its own keywords.
+        ``return_token_timestamps``: element i is {"text": that, "tokens": the clip's token ids, "token_timestamps":
+        one time in seconds per token} (generate_batch's token timestamps: subtitles, or when a keyword was said)."""
         N = input_features.size(0)
         oracles = [[] for _ in range(N)] if oracles is None else [list(o) for o in oracles]
         if len(oracles) != N:
             raise ValueError(f"transcribe_batch needs one oracle list per clip ({N}), got {len(oracles)}")
+        more = {"return_token_timestamps": True} if return_token_timestamps else {}
         preds = self.whisper.generate_batch(input_features, task="transcribe", language=self.language,
                                             return_timestamps=False, num_beams=self.num_beams,
-                                            keyword_spotting=self._keyword_spotting_clips(oracles))
+                                            keyword_spotting=self._keyword_spotting_clips(oracles), **more)
         self.oracle_buffer = list(oracles[-1]) if oracles else []   # where the loop of forward calls leaves it
-        return [self._to_text(p[0].tolist()) for p in preds]
+        if not return_token_timestamps:
+            return [self._to_text(p[0].tolist()) for p in preds]
+        return [{"text": self._to_text(p["sequences"][0].tolist()), "tokens": p["sequences"][0].tolist(),
+                 "token_timestamps": p["token_timestamps"][0].tolist()} for p in preds]
 
     # ------------------------------------------------------------------ evaluation (cb_whisper.py:212-289)
     def on_test_epoch_start(self):

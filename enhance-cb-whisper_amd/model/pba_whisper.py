@@ -435,7 +435,8 @@ class PBAWhisper:
     def generate_batch(self, input_features: torch.Tensor, task: Optional[str] = None, language: Optional[str] = None,
                        return_timestamps: Optional[bool] = None, num_beams: int = 1,
                        max_new_tokens: Optional[int] = None, length_penalty: float = 1.0,
-                       keyword_spotting: Optional[Callable] = None) -> List[torch.Tensor]:
+                       keyword_spotting: Optional[Callable] = None, return_token_timestamps: bool = False,
+                       num_frames: Optional[int] = None) -> List:
         """A batch of short clips in one call: input_features [N, n_mel, T <= 3000] -> N LongTensors [1, n_i], element
         i equal to ``generate(input_features[i:i + 1], ...)`` with the same arguments (the reference, and generate,
         take one clip of 30 s or less at a time, pba_whisper.py:283-338).  One ``keyword_spotting`` call over all
@@ -448,9 +449,19 @@ class PBAWhisper:
         (ValueError: long-form is generate's), ``language=None`` on a multilingual checkpoint (NotImplementedError:
         the free language position runs on the host search), more than 16 beams, and a forced prefix of a single
         token (both NotImplementedError: generate decodes those on the host loop).  Sampling and the temperature
-        fallback are generate's."""
+        fallback are generate's.
+        ``return_token_timestamps`` (what generate cannot give a short clip: the reference's short-form return fails
+        on the ModelOutput, pba_whisper.py:338): element i is {"sequences": the LongTensor [1, n_i] above,
+        "token_timestamps": FloatTensor [1, n_i]}, the token timestamps of the clip's full decoded row (prefix
+        included; ``token_timestamps_batch`` over the encoder outputs the call already holds, ``num_frames`` as in
+        generate) sliced as the tokens are.  A checkpoint without alignment heads raises generate's ValueError before
+        the spotting call and any GPU work."""
         if input_features is None or input_features.dim() != 3:
             raise ValueError("PBAWhisper.generate_batch needs input_features [N, n_mel, T]")
+        if return_token_timestamps and not self.alignment_heads:   # 4.37.2 _set_num_frames, as generate
+            raise ValueError("Model generation config has no `alignment_heads`, token-level timestamps not available. "
+                             "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this "
+                             "property to the generation config.")
         N, _, T = input_features.shape
         if T > N_FRAMES:
             raise ValueError("PBAWhisper.generate_batch takes clips of at most 3000 mel frames (30 seconds); long-form "
@@ -485,7 +496,11 @@ class PBAWhisper:
             bias_ats = [(lambda pos, b=b: bias_begin if pos == b else bias) for b in begins]
             seqs = self.decoder.beam_search_windows(windows, num_beams, self.tokens.eot, limits, bias_ats, rules, begins,
                                                     1, length_penalty=length_penalty, max_rows=80)
-        return [torch.tensor([list(q)[len(p):]], dtype=torch.long) for q, p in zip(seqs, prompts)]
+        out = [torch.tensor([list(q)[len(p):]], dtype=torch.long) for q, p in zip(seqs, prompts)]
+        if not return_token_timestamps:
+            return out
+        times = self.token_timestamps_batch([w[0] for w in windows], [list(q) for q in seqs], num_frames)
+        return [{"sequences": o, "token_timestamps": t[None, len(p):]} for o, t, p in zip(out, times, prompts)]
 
     # a caller's transformers generation controls this build restates (the reference forwards
     # **kwargs into GenerationMixin.generate, pba_whisper.py:320-331), pinned by tests/golden/gen_controls_micro.npz
@@ -672,6 +687,42 @@ class PBAWhisper:
         w = self.decoder.cross_attn_probs(row[:-1], alignment_pairs(self.alignment_heads))
         extract = extract_token_timestamps_dev if _dev_token_ts() else extract_token_timestamps
         return extract(w, self.median_filter_width, 0.02, num_frames, variant, num_input_ids)
+
+    def token_timestamps_batch(self, enc_outs: Sequence[torch.Tensor], rows: Sequence[Sequence[int]],
+                               num_frames=None, variant: str = "4.37", num_input_ids=None) -> List[torch.Tensor]:
+        """``token_timestamps`` for several decoded rows at once, row i against the encoder output enc_outs[i]
+        [1500, D] (or [1, 1500, D]) of its window: a list of float32 [len(rows[i])].  The weights of all rows come from
+        one lock-step decoder state (DecoderEngine.cross_attn_probs_windows), the alignment matrices and the DTWs from
+        one batched pass with one copy back (cbw.token_timestamps.extract_token_timestamps_batch_dev); with
+        CBW_DEV_TOKEN_TS=0, extract_token_timestamps per row.  ``num_frames`` / ``num_input_ids``: one value, or one
+        per row.  Each row's result equals ``token_timestamps`` on its window."""
+        from cbw.token_timestamps import (alignment_pairs, extract_token_timestamps,
+                                          extract_token_timestamps_batch_dev)
+        if not self.alignment_heads:
+            raise ValueError("token-level timestamps need the checkpoint's alignment_heads")
+        if len(enc_outs) != len(rows):
+            raise ValueError("token_timestamps_batch needs one encoder output per row")
+        rows = [[int(t) for t in row] for row in rows]
+        N = len(rows)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * N   # noqa: E731
+        nf, ni = per(num_frames), per(num_input_ids)
+        if len(nf) != N or len(ni) != N:
+            raise ValueError("num_frames / num_input_ids: one value per row, or one for all")
+        out = [torch.zeros(len(row), dtype=torch.float32) for row in rows]
+        keep = [i for i, row in enumerate(rows) if len(row) >= 2]
+        if not keep:
+            return out
+        ws = self.decoder.cross_attn_probs_windows([(enc_outs[i], rows[i][:-1]) for i in keep],
+                                                   alignment_pairs(self.alignment_heads))
+        if _dev_token_ts():
+            got = extract_token_timestamps_batch_dev(ws, self.median_filter_width, 0.02, [nf[i] for i in keep], variant,
+                                                     [ni[i] for i in keep])
+        else:
+            got = [extract_token_timestamps(w, self.median_filter_width, 0.02, nf[i], variant, ni[i])
+                   for w, i in zip(ws, keep)]
+        for i, t in zip(keep, got):
+            out[i] = t
+        return out
 
     @staticmethod
     def _segment_out(s_):

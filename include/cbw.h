@@ -466,6 +466,45 @@ int cbw_align_matrix(const float* probs, int n, int T_all, int t0, int T, int F,
                      int32_t* degenerate, void* ws, int64_t ws_bytes, cbw_stream_t stream);
 int cbw_dtw_dev(const float* matrix, int T, int F, int32_t* first_frame, int32_t* text_idx, int32_t* time_idx,
                 int32_t* len, void* ws, int64_t ws_bytes, cbw_stream_t stream);
+/* Token-level timestamps for a batch of decoded rows (a batch of short clips, cbw_decoder_step_wide's callers: what
+ * transformers' _extract_token_timestamps, reached from pba_whisper.py:333-336 and 425-442, gives each row; the
+ * reference takes one clip per call, so the batching has no counterpart there).
+ * cbw_decoder_cross_attn_probs_slot: cbw_decoder_cross_attn_probs against encoder slot `slot` of a lock-step state
+ *   (cbw_decoder_cross_kv_slot first), the row's self-attention K/V written into cache row r0; the other slots'
+ *   cross K/V and the other rows' self K/V are not touched.  The arithmetic follows T alone -- not B, Benc, slot or
+ *   r0 -- so the probabilities equal, bit for bit, those of cbw_decoder_cross_attn_probs on a one-window state with
+ *   the same encoder output.  One call per window: several windows' rows in one GEMM pass would change the tile
+ *   and split-K choice, which follows the row count.  CBW_ERR_INVALID before any GPU work for what
+ *   cbw_decoder_cross_attn_probs refuses and for slot outside [0, Benc) or r0 outside [0, B).
+ * cbw_align_matrix_batch / cbw_dtw_dev_batch: cbw_align_matrix and cbw_dtw_dev (without the path) for N windows,
+ *   1 <= N <= CBW_TOKEN_TS_MAX_WINDOWS, in one launch each: the windows' table `win` (host memory, read during the
+ *   call) goes to the kernel by value, the window is a coordinate of the grid, and the alignment matrix, the DTW
+ *   wavefront and the trace of a window are those of the single-window calls bit for bit.  Window i reads
+ *   probs + probs_off (f32 [n][T_all][1500]), writes matrix + matrix_off (f32 [T][F]) and keeps its trace at
+ *   (char*)ws + ws_off; probs_off and matrix_off count floats, ws_off counts bytes and is a multiple of 4; none is
+ *   negative; the caller keeps the windows' ranges apart.  n heads and the median width are shared.
+ *   degenerate int32 [N]: window i's flag (a flagged window's outputs are not to be used; the others' are not
+ *   disturbed).  first_frame int32 [N][ld], ld >= the largest T: row i holds window i's T jump frames.
+ *   cbw_token_ts_ws_bytes_batch: the bytes of ws for the table packed back to back, the sum of the windows'
+ *   cbw_token_ts_ws_bytes(T, F) (each a multiple of 4, the alignment of ws_off); -1 as the calls refuse.
+ *   Nothing allocates or synchronises.  CBW_ERR_INVALID before any GPU work, per window, for what the single-window
+ *   entries refuse (T < 2 for the matrix, T < 1 for the DTW, T > 1024, F outside [1, 1500], t0 < 0 or t0 + T > T_all,
+ *   n < 1, an even width or one above 7, a null pointer, ws misaligned or ws_off + the window's bytes > ws_bytes),
+ *   and for N out of range, a negative offset, a ws_off that is no multiple of 4, ld below the largest T.        */
+#define CBW_TOKEN_TS_MAX_WINDOWS 16
+typedef struct {
+    int32_t T_all, t0, T, F;
+    int64_t probs_off, matrix_off;   /* floats */
+    int64_t ws_off;                  /* bytes, a multiple of 4 */
+} cbw_token_ts_window;
+int cbw_decoder_cross_attn_probs_slot(cbw_decoder* h, const int32_t* tokens, int T, const int32_t* heads, int n,
+                                      int slot, int r0, int B, int Benc, void* state, int64_t state_bytes,
+                                      float* probs, cbw_stream_t stream);
+int64_t cbw_token_ts_ws_bytes_batch(const cbw_token_ts_window* win, int N);
+int cbw_align_matrix_batch(const float* probs, int n, const cbw_token_ts_window* win, int N, int width, float* matrix,
+                           int32_t* degenerate, void* ws, int64_t ws_bytes, cbw_stream_t stream);
+int cbw_dtw_dev_batch(const float* matrix, const cbw_token_ts_window* win, int N, int32_t* first_frame, int ld,
+                      void* ws, int64_t ws_bytes, cbw_stream_t stream);
 int cbw_decoder_reorder(cbw_decoder* h, const int32_t* src_rows, int B, int Benc, int len, void* state,
                         int64_t state_bytes, cbw_stream_t stream);
 /* HF beam-search scores: log_softmax(logits) + bias, and their top-k (k <= 16, ties -> lower id) per
