@@ -138,6 +138,10 @@ SIGNATURES = {
     "cbw_linear_rows_wide_kernel": (c_char_p, [c_int, c_int, c_int, c_int]),
     "cbw_layernorm_rows": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p]),
     "cbw_encoder_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "cbw_decode_attention_ws_floats": (c_int64, [c_int, c_int]),
+    "cbw_decode_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int,
+                                     c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "cbw_decode_cross_probs": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cbw_kws_profile": (c_int, [c_void_p, c_int]),
     "cbw_decoder_create": (c_int, [ctypes.POINTER(DecoderConfig), ctypes.POINTER(c_void_p)]),
     "cbw_decoder_destroy": (c_int, [c_void_p]),

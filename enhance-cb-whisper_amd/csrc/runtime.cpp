@@ -2915,17 +2915,29 @@ bool dec_self_one_launch() {   // CBW_DEC_SELF_ONE=0: self-attention on the spli
     const char* e = getenv("CBW_DEC_SELF_ONE");
     return !(e && atoi(e) == 0);
 }
-hipError_t dec_attend(const DecState& s, const uint16_t* q, int ldq, const uint16_t* kc, const uint16_t* vc,
+// the kernel a step's attention runs on (the only statement of the routing: dec_attend launches what this names,
+// cbw_decode_attention asks it which operands a call needs)
+enum class DecAttn { SelfOne, Row, Split };
+DecAttn dec_attend_route(int n_keys, int rows_per_kv, bool has_pos, bool self) {
+    if (self && rows_per_kv == 1 && n_keys <= 448 && dec_split_enabled() && dec_self_one_launch())
+        return DecAttn::SelfOne;
+    if (self && !has_pos && n_keys <= dec_self_split_keys()) return DecAttn::Row;
+    if (has_pos || (dec_split_enabled() && rows_per_kv <= 8)) return DecAttn::Split;
+    return DecAttn::Row;
+}
+// part: cbw_dec_attn_split_floats(B, H) floats, the split kernel's partials (the state's apart)
+hipError_t dec_attend(float* part, const uint16_t* q, int ldq, const uint16_t* kc, const uint16_t* vc,
                       int64_t kv_bstride, int n_keys, int rows_per_kv, uint16_t* out, int B, int H, int D,
                       hipStream_t st, const int* n_keys_pos = nullptr, bool self = false, int nk_rows = 0) {
-    if (self && rows_per_kv == 1 && n_keys <= 448 && dec_split_enabled() && dec_self_one_launch())
+    switch (dec_attend_route(n_keys, rows_per_kv, n_keys_pos != nullptr, self)) {
+    case DecAttn::SelfOne:
         return cbw_dec_self_attn(q, ldq, kc, vc, kv_bstride, n_keys, out, B, H, D, st, n_keys_pos, nk_rows);
-    if (self && !n_keys_pos && n_keys <= dec_self_split_keys())
+    case DecAttn::Split:
+        return cbw_dec_attn_split(q, ldq, kc, vc, kv_bstride, n_keys, rows_per_kv, out, B, H, D, part, st, n_keys_pos,
+                                  nk_rows);
+    default:
         return cbw_dec_attention(q, ldq, kc, vc, kv_bstride, n_keys, rows_per_kv, out, B, H, D, st);
-    if (n_keys_pos || (dec_split_enabled() && rows_per_kv <= 8))
-        return cbw_dec_attn_split(q, ldq, kc, vc, kv_bstride, n_keys, rows_per_kv, out, B, H, D, s.apart, st,
-                                  n_keys_pos, nk_rows);
-    return cbw_dec_attention(q, ldq, kc, vc, kv_bstride, n_keys, rows_per_kv, out, B, H, D, st);
+    }
 }
 }  // namespace
 
@@ -3064,13 +3076,13 @@ int dec_step(cbw_decoder* h, const int32_t* tokens, int pos, const int32_t* pos_
         uint16_t* vl = s.vs + l * self_per;
         const KvAppend kv{kl, vl, (int64_t)ML * D, D, pos, pos_dev, pos_rows};
         CHK(attn_block(run, L.ln1, L.qkv, L.out, s.h, s.qkv, s.att, kv, [&]() -> int {
-            HIPCHK(dec_attend(s, s.qkv, 3 * D, kl, vl, (int64_t)ML * D, pos_dev ? ML : pos + 1, 1, s.att, B, H, D, st,
-                              pos_dev, true, pos_rows));
+            HIPCHK(dec_attend(s.apart, s.qkv, 3 * D, kl, vl, (int64_t)ML * D, pos_dev ? ML : pos + 1, 1, s.att, B, H, D,
+                              st, pos_dev, true, pos_rows));
             return CBW_OK;
         }));
         CHK(attn_block(run, L.ln_x, L.cq, L.co, s.h, s.qc, s.att, {}, [&]() -> int {
-            HIPCHK(dec_attend(s, s.qc, D, s.kc + l * cross_per, s.vc + l * cross_per, (int64_t)1500 * D, 1500,
-                              B / Benc, s.att, B, H, D, st));
+            HIPCHK(dec_attend(s.apart, s.qc, D, s.kc + l * cross_per, s.vc + l * cross_per, (int64_t)1500 * D,
+                              1500, B / Benc, s.att, B, H, D, st));
             return CBW_OK;
         }));
         CHK(mlp_block(run, L, s.h, s.f));
@@ -3497,6 +3509,69 @@ int cbw_gemm_splitk_factor(int M, int K, int N) {
 int cbw_encoder_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int H, cbw_stream_t stream) {
     if (!qkv || !out || B <= 0 || T <= 0 || H <= 0) return fail(CBW_ERR_INVALID, "cbw_encoder_attention: bad argument");
     HIPCHK(cbw_attention(qkv, out, B, T, H, 64, (hipStream_t)stream));
+    return CBW_OK;
+}
+
+int64_t cbw_decode_attention_ws_floats(int B, int H) {
+    if (B <= 0 || H <= 0 || (int64_t)B * H > INT32_MAX / cbw_dec_attn_split_floats(1, 1))
+        return fail(CBW_ERR_INVALID, "cbw_decode_attention_ws_floats: bad shape");
+    return cbw_dec_attn_split_floats(B, H);
+}
+
+int cbw_decode_attention(const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int64_t kv_bstride,
+                         int n_keys, int rows_per_kv, const int32_t* n_keys_pos, int nk_rows, int causal, int path,
+                         uint16_t* out, int B, int H, int D, float* ws, int64_t ws_floats, cbw_stream_t stream) {
+    auto bad = [](const char* why) { return fail(CBW_ERR_INVALID, std::string("cbw_decode_attention: ") + why); };
+    if (!q || !k || !v || !out) return bad("null operand");
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return bad("q, k, v must be 16-byte aligned");
+    if (path < 0 || path > 4) return bad("path must be 0..4");
+    if (B <= 0 || H <= 0) return bad("B, H must be positive");
+    if ((int64_t)H * 64 > D || D % 8) return bad("D must be a multiple of 8 and at least 64 H");
+    if (ldq % 8 || ldq < H * 64) return bad("ldq must be a multiple of 8 and at least 64 H");
+    if (n_keys < 1 || n_keys > (path == 4 ? 448 : 1536)) return bad("n_keys must be 1..1536 (1..448 on path 4)");
+    if (kv_bstride % 8 || kv_bstride < (int64_t)n_keys * D)
+        return bad("kv_bstride must be a multiple of 8 and at least n_keys D");
+    if (rows_per_kv < 1 || B % rows_per_kv) return bad("rows_per_kv must be positive and divide B");
+    if (path == 4 && rows_per_kv != 1) return bad("path 4 needs rows_per_kv == 1");
+    if (causal && path != 2) return bad("causal needs path 2");
+    if (n_keys_pos && path == 2) return bad("path 2 takes no device key counts");
+    const bool routed = path < 2;   // paths 0 and 1: the step's routing decides, self-attention on path 0
+    const bool split = path == 3 || (routed && dec_attend_route(n_keys, rows_per_kv, n_keys_pos != nullptr, path == 0) ==
+                                                   DecAttn::Split);
+    if (split && rows_per_kv > 8) return bad("the split kernel serves at most 8 rows per K/V batch");
+    if (split) {
+        const int64_t need = cbw_decode_attention_ws_floats(B, H);
+        if (need < 0) return bad("B H too large for the split kernel's partials");
+        if (!ws || ws_floats < need) return bad("ws null or too small");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    switch (path) {
+    case 2:
+        HIPCHK(cbw_dec_attention(q, ldq, k, v, kv_bstride, n_keys, rows_per_kv, out, B, H, D, st, causal != 0));
+        break;
+    case 3:
+        HIPCHK(cbw_dec_attn_split(q, ldq, k, v, kv_bstride, n_keys, rows_per_kv, out, B, H, D, ws, st, n_keys_pos,
+                                  nk_rows != 0));
+        break;
+    case 4:
+        HIPCHK(cbw_dec_self_attn(q, ldq, k, v, kv_bstride, n_keys, out, B, H, D, st, n_keys_pos, nk_rows != 0));
+        break;
+    default:
+        HIPCHK(dec_attend(ws, q, ldq, k, v, kv_bstride, n_keys, rows_per_kv, out, B, H, D, st, n_keys_pos, path == 0,
+                          nk_rows != 0));
+    }
+    return CBW_OK;
+}
+
+int cbw_decode_cross_probs(const uint16_t* q, int ldq, const uint16_t* k, int n_keys, int T, int D, int head,
+                           float* out, cbw_stream_t stream) {
+    if (!q || !k || !out || ((uintptr_t)k & 15))
+        return fail(CBW_ERR_INVALID, "cbw_decode_cross_probs: null operand or k not 16-byte aligned");
+    if (n_keys < 1 || n_keys > 1536 || T <= 0 || head < 0 || D % 8 || (int64_t)(head + 1) * 64 > D ||
+        (int64_t)(head + 1) * 64 > ldq)
+        return fail(CBW_ERR_INVALID,
+                    "cbw_decode_cross_probs: 1 <= n_keys <= 1536, T >= 1, D % 8, 64 (head + 1) <= D, ldq");
+    HIPCHK(cbw_dec_cross_probs(q, ldq, k, n_keys, T, D, head, out, (hipStream_t)stream));
     return CBW_OK;
 }
 

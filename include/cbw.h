@@ -647,6 +647,28 @@ int cbw_layernorm_rows(const float* x, const float* g, const float* b, uint16_t*
 /* The encoder's self-attention (HF WhisperAttention under src/model/cb_whisper.py:100-104, non-causal, head dim
  * 64): qkv bf16 [B][T][3][H][64] with q pre-scaled by 1/8 -> out bf16 [B][T][H * 64], softmax in fp32. */
 int cbw_encoder_attention(const uint16_t* qkv, uint16_t* out, int B, int T, int H, cbw_stream_t stream);
+/* The decoder's attention kernels one by one (building blocks for the tests): out bf16 [B][D] (columns [0, 64 H)
+ * written) = softmax_j(q_r . k_j) v_j per row r and head h, head dim 64, q pre-scaled, softmax in fp32; asynchronous.
+ *   q bf16, row r at q + r * ldq (ldq = 3 D: the q slots of fused qkv rows); k, v bf16: key j, column c of K/V batch b
+ *     at b * kv_bstride + j * D + c; row r reads batch r / rows_per_kv.
+ *   keys: row r sees keys [0, n), n = n_keys; with n_keys_pos (device int32; paths 0, 1, 3, 4) n = min(n_keys,
+ *     n_keys_pos[i] + 1), i = 0 (nk_rows 0) or the row's K/V batch (nk_rows 1), and every entry must be >= 0; with
+ *     causal (path 2 only: the prefill) n = min(n_keys, r + 1).
+ *   path: 0 what cbw_decoder_step* launches for self-attention and 1 for cross-attention (the step's own routing
+ *     function, switches CBW_DEC_SPLIT, CBW_DEC_SELF_ONE, CBW_DEC_SELF_SPLIT read per call); 2 dec_attention_kernel, a
+ *     workgroup per (row, head), n_keys <= 1536; 3 dec_attn_split_kernel + dec_attn_combine_kernel, 64-key chunks,
+ *     rows_per_kv <= 8, n_keys <= 1536; 4 dec_self_attn_kernel, one launch, rows_per_kv == 1, n_keys <= 448.
+ *   ws: cbw_decode_attention_ws_floats(B, H) floats (-1 on a bad shape), needed wherever the split kernel may run.
+ * D, ldq, kv_bstride % 8 == 0, D >= 64 H, ldq >= 64 H, kv_bstride >= n_keys * D, B % rows_per_kv == 0; q, k, v 16-byte
+ * aligned.  Every check comes before any GPU work. */
+int64_t cbw_decode_attention_ws_floats(int B, int H);
+int cbw_decode_attention(const uint16_t* q, int ldq, const uint16_t* k, const uint16_t* v, int64_t kv_bstride,
+                         int n_keys, int rows_per_kv, const int32_t* n_keys_pos, int nk_rows, int causal, int path,
+                         uint16_t* out, int B, int H, int D, float* ws, int64_t ws_floats, cbw_stream_t stream);
+/* dec_cross_probs_kernel (the weights behind token-level timestamps): out f32 [T][n_keys] = softmax_j(q_r . k_j) of
+ * head `head`; q rows of pitch ldq, k [n_keys][D]; 1 <= n_keys <= 1536, D % 8 == 0, 64 (head + 1) <= D and <= ldq. */
+int cbw_decode_cross_probs(const uint16_t* q, int ldq, const uint16_t* k, int n_keys, int T, int D, int head,
+                           float* out, cbw_stream_t stream);
 
 /* The kernels of the exact-decision tiers (cbw_kws_rescore, cbw_kws_rescore_x3, cbw_kws_calibrate_bias) one by one
  * (building blocks for the tests): each entry checks its arguments and calls the launcher the tier itself calls, so a
