@@ -444,8 +444,137 @@ CBW_DEV uint32_t pk_max_u16(uint32_t a, uint32_t b) {
     const u16x2 r = __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b));
     return __builtin_bit_cast(uint32_t, r);
 }
+// m = max(m, v & mask) over the 8 u16 lanes of a 16-byte vector
+CBW_DEV void pk_max_u16x4(uint4& m, const uint4& v, uint32_t mask = 0xffffffffu) {
+    m.x = pk_max_u16(m.x, v.x & mask);
+    m.y = pk_max_u16(m.y, v.y & mask);
+    m.z = pk_max_u16(m.z, v.z & mask);
+    m.w = pk_max_u16(m.w, v.w & mask);
+}
 
 constexpr int SP_LOADS = ((4 * SP_RMAX + 7) * SP_IC + 255) / 256;   // patch pixels per thread (max)
+
+// The passages below are shared by the fused kernels (stem_pool_kernel V1 / V2, stem_pool_v3_kernel and, where noted,
+// stem16_pool_kernel); stem_kernel and maxpool3s2_kernel, the unfused path the tests compare them with, use none.
+//
+// sp_tile_origin: tile t of N x nrt x nct (pair, row tile of R pooled rows, column tile of SP_PW pooled columns).
+// The inputs come by reference, as the kernels' own lambdas captured them: by value the X3 stem compiled to other
+// instructions than it had.
+CBW_DEV void sp_tile_origin(int t, const int& ntiles, const int& nrt, const int& nct, const int& R, int& n, int& ph0,
+                            int& pw0) {
+    t = xcd_remap(t, ntiles);
+    n = t / (nrt * nct);
+    const int rem = t - n * (nrt * nct);
+    const int rt = rem / nct;
+    ph0 = rt * R;
+    pw0 = (rem - rt * nct) * SP_PW;
+}
+
+// stem_load_bias: the lane's 4 x 4 output channels' bias, and stem_load_weights: its A fragments of all 7 tap rows
+// before it, kept in registers over the block's tiles.
+// r06: retire the weight / bias loads here.  Without this wait the compiler's counters treat them as possibly
+// pending at the loop header (merged with the preheader), so every tile's first fragment waited vmcnt(4) and its
+// epilogue vmcnt(0) -- i.e. for the NEXT tile's patch loads issued just before: the prefetch was exposed.
+CBW_DEV void stem_load_bias(const float* __restrict__ bias, int fq, f32x4 (&bv)[4]) {
+#pragma unroll
+    for (int jn = 0; jn < 4; ++jn) bv[jn] = *(const f32x4*)(bias + jn * 16 + fq * 4);
+    __builtin_amdgcn_s_waitcnt(0);
+}
+CBW_DEV void stem_load_weights(const bf16* __restrict__ w, const float* __restrict__ bias, int fr, int fq,
+                               bf16x8 (&wv)[7][4], f32x4 (&bv)[4]) {
+#pragma unroll
+    for (int kh = 0; kh < 7; ++kh)
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn) wv[kh][jn] = *(const bf16x8*)(w + (jn * 16 + fr) * 224 + kh * 32 + fq * 8);
+    stem_load_bias(bias, fq, bv);
+}
+
+// stem_frag_mma: one fragment (16 stem pixels x 64 channels) from the patch in LDS: xa = the lane's pixel pair of tap
+// row 0, the tap rows SP_IC pixels apart; 7 tap rows x 4 channel blocks of MFMA 16x16x32, kh ascending.
+CBW_DEV void stem_frag_mma(const char* xa, const bf16x8 (&wv)[7][4], f32x4 (&acc)[4]) {
+#pragma unroll
+    for (int jn = 0; jn < 4; ++jn) acc[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kh = 0; kh < 7; ++kh) {
+        const bf16x8 xv = *(const bf16x8*)(xa + kh * SP_IC * 8);
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn) acc[jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[kh][jn], xv, acc[jn], 0, 0, 0);
+    }
+}
+
+// stem_relu_pack, the V2 epilogue of one fragment lane: bias, round to bf16 pairs, ReLU on the rounded pairs
+// (v_cvt_pk_bf16_f32 + v_pk_max_i16: no negative and no -0 entries), 8-byte stores of the lane's 4 channels of each
+// channel block at dst + 32 jn; zeros where the pixel lies outside the stem image.
+CBW_DEV void stem_relu_pack(const f32x4 (&acc)[4], const f32x4 (&bv)[4], char* dst, bool inside) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int jn = 0; jn < 4; ++jn) {
+        uint32_t o[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            s16x2 v = __builtin_bit_cast(s16x2, __builtin_convertvector(
+                (f32x2{acc[jn][2 * h] + bv[jn][2 * h], acc[jn][2 * h + 1] + bv[jn][2 * h + 1]}), bf16x2));
+            o[h] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(v, s16x2{0, 0}));
+        }
+        *(uint2*)(dst + jn * 32) = inside ? make_uint2(o[0], o[1]) : make_uint2(0u, 0u);
+    }
+}
+
+// stem_pool_pairs, the V2 pool of a tile (stem tile S of SR rows, no sign bits set): item = (pooled row pair, column,
+// 8-channel group), stem rows 4 pr2 .. + 4, each row's 3-column max once (5 stem rows: 15 reads for 2 outputs).
+CBW_DEV void stem_pool_pairs(const char* S, bf16* y, int n, int ph0, int pw0, int R, int SR, int Hp, int Wp) {
+    const int NR2 = (R + 1) / 2;
+    for (int i = threadIdx.x; i < NR2 * SP_PW * 8; i += 256) {
+        const int cg = i & 7, pix = i >> 3;
+        const int pr2 = pix / SP_PW, pc = pix - pr2 * SP_PW;
+        const int pw = pw0 + pc;
+        if (pw >= Wp) continue;
+        uint4 cm[5];
+#pragma unroll
+        for (int dr = 0; dr < 5; ++dr) {
+            const int sr = 4 * pr2 + dr;
+            uint4 m = make_uint4(0u, 0u, 0u, 0u);
+            if (sr < SR) {
+#pragma unroll
+                for (int dc = 0; dc < 3; ++dc)
+                    pk_max_u16x4(m, *(const uint4*)(S + (sr * SP_SC + 2 * pc + dc) * SP_SPITCH + cg * 16));
+            }
+            cm[dr] = m;
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int pr = 2 * pr2 + k, ph = ph0 + pr;
+            if (pr >= R || ph >= Hp) break;
+            uint4 m = cm[2 * k];
+            pk_max_u16x4(m, cm[2 * k + 1]);
+            pk_max_u16x4(m, cm[2 * k + 2]);
+            *(uint4*)(y + (((int64_t)n * Hp + ph) * Wp + pw) * 64 + cg * 8) = m;
+        }
+    }
+}
+
+// stem_pool_masked, the V1 pool of a tile (bf16 stem tile S; also the 16-channel kernel's): item = (pooled row,
+// column, 8-channel group), 3x3/s2 max.  Every stem value is a ReLU output (>= 0, possibly -0): with the sign bit
+// cleared the bf16 bit patterns order like the values, so the max runs as packed u16 max.
+CBW_DEV void stem_pool_masked(const char* S, bf16* y, int n, int ph0, int pw0, int R, int Hp, int Wp) {
+    for (int i = threadIdx.x; i < R * SP_PW * 8; i += 256) {
+        const int cg = i & 7, pix = i >> 3;
+        const int pr = pix / SP_PW, pc = pix - pr * SP_PW;
+        const int ph = ph0 + pr, pw = pw0 + pc;
+        if (ph >= Hp || pw >= Wp) continue;
+        uint4 m = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int dr = 0; dr < 3; ++dr)
+#pragma unroll
+            for (int dc = 0; dc < 3; ++dc) {
+                const uint4 v = *(const uint4*)(S + ((2 * pr + dr) * SP_SC + 2 * pc + dc) * SP_SPITCH + cg * 16);
+                pk_max_u16x4(m, v, 0x7fff7fffu);
+            }
+        *(uint4*)(y + (((int64_t)n * Hp + ph) * Wp + pw) * 64 + cg * 8) = m;
+    }
+}
 
 // V2 (issue diet, SQ r05a: the stem's waves issue VALU 41 % of their cycles against 31 % MFMA busy): the stem tile's
 // ReLU on the rounded bf16 pairs (v_cvt_pk_bf16_f32 + v_pk_max_i16: no negative and no -0 entries), so the max-pool
@@ -467,26 +596,10 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16* __restric
     const int ntiles = N * nrt * nct;
     const int fr = lane & 15, fq = lane >> 4;
     bf16x8 wv[7][4];
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) wv[kh][jn] = *(const bf16x8*)(w + (jn * 16 + fr) * 224 + kh * 32 + fq * 8);
     f32x4 bv[4];
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn) bv[jn] = *(const f32x4*)(bias + jn * 16 + fq * 4);
-    // r06: retire the weight / bias loads here.  Without this wait the compiler's counters treat them as possibly
-    // pending at the loop header (merged with the preheader), so every tile's first fragment waited vmcnt(4) and its
-    // epilogue vmcnt(0) -- i.e. for the NEXT tile's patch loads issued just before: the prefetch was exposed.
-    __builtin_amdgcn_s_waitcnt(0);
+    stem_load_weights(w, bias, fr, fq, wv, bv);
 
-    auto tile_origin = [&](int t, int& n, int& ph0, int& pw0) {
-        t = xcd_remap(t, ntiles);
-        n = t / (nrt * nct);
-        const int rem = t - n * (nrt * nct);
-        const int rt = rem / nct;
-        ph0 = rt * R;
-        pw0 = (rem - rt * nct) * SP_PW;
-    };
+    auto tile_origin = [&](int t, int& n, int& ph0, int& pw0) { sp_tile_origin(t, ntiles, nrt, nct, R, n, ph0, pw0); };
     uint2 pv[SP_LOADS];
     auto load_patch = [&](int t) {
         int n, ph0, pw0;
@@ -523,26 +636,16 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16* __restric
             const int srr = pp / SP_SC, scc = pp - srr * SP_SC;
             const int gr = sr0 + srr, gc = sc0 + scc;
             const bool ok = gr >= 0 && gr < Hs && gc >= 0 && gc < Ws;
+            char* sw = S + pp * SP_SPITCH + fq * 8;
+            if constexpr (V2) {
+                stem_relu_pack(acc, bv, sw, ok);
+            } else {
 #pragma unroll
-            for (int jn = 0; jn < 4; ++jn) {
-                if constexpr (V2) {
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-                    typedef short s16x2 __attribute__((ext_vector_type(2)));
-                    uint32_t o[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        s16x2 v = __builtin_bit_cast(s16x2, __builtin_convertvector(
-                            (f32x2{acc[jn][2 * h] + bv[jn][2 * h], acc[jn][2 * h + 1] + bv[jn][2 * h + 1]}), bf16x2));
-                        o[h] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(v, s16x2{0, 0}));
-                    }
-                    *(uint2*)(S + pp * SP_SPITCH + (jn * 16 + fq * 4) * 2) = ok ? make_uint2(o[0], o[1])
-                                                                                 : make_uint2(0u, 0u);
-                } else {
+                for (int jn = 0; jn < 4; ++jn) {
                     bf16x4 o;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) o[q] = f2bf(ok ? fmaxf(acc[jn][q] + bv[jn][q], 0.f) : 0.f);
-                    *(bf16x4*)(S + pp * SP_SPITCH + (jn * 16 + fq * 4) * 2) = o;
+                    *(bf16x4*)(sw + jn * 32) = o;
                 }
             }
         };
@@ -552,79 +655,15 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16* __restric
             return In + ((2 * sr) * SP_IC + 2 * sc + 2 * fq) * 8;
         };
         for (int f = wid; f * 16 < P; f += 4) {
-            const char* xa = frag_addr(f);
             f32x4 acc[4];
-#pragma unroll
-            for (int jn = 0; jn < 4; ++jn) acc[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kh = 0; kh < 7; ++kh) {
-                const bf16x8 xv = *(const bf16x8*)(xa + kh * SP_IC * 8);
-#pragma unroll
-                for (int jn = 0; jn < 4; ++jn)
-                    acc[jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[kh][jn], xv, acc[jn], 0, 0, 0);
-            }
+            stem_frag_mma(frag_addr(f), wv, acc);
             epi(f, acc);
         }
         __syncthreads();
-        if constexpr (V2) {
-            // item = (pooled row pair, column, 8-channel group): stem rows 4 pr2 .. + 4, each row's 3-column max once
-            const int NR2 = (R + 1) / 2;
-            for (int i = tid; i < NR2 * SP_PW * 8; i += 256) {
-                const int cg = i & 7, pix = i >> 3;
-                const int pr2 = pix / SP_PW, pc = pix - pr2 * SP_PW;
-                const int pw = pw0 + pc;
-                if (pw >= Wp) continue;
-                uint4 cm[5];
-#pragma unroll
-                for (int dr = 0; dr < 5; ++dr) {
-                    const int sr = 4 * pr2 + dr;
-                    uint4 m = make_uint4(0u, 0u, 0u, 0u);
-                    if (sr < SR) {
-#pragma unroll
-                        for (int dc = 0; dc < 3; ++dc) {
-                            const uint4 v = *(const uint4*)(S + (sr * SP_SC + 2 * pc + dc) * SP_SPITCH + cg * 16);
-                            m.x = pk_max_u16(m.x, v.x);
-                            m.y = pk_max_u16(m.y, v.y);
-                            m.z = pk_max_u16(m.z, v.z);
-                            m.w = pk_max_u16(m.w, v.w);
-                        }
-                    }
-                    cm[dr] = m;
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int pr = 2 * pr2 + k, ph = ph0 + pr;
-                    if (pr >= R || ph >= Hp) break;
-                    uint4 m = cm[2 * k];
-                    m.x = pk_max_u16(pk_max_u16(m.x, cm[2 * k + 1].x), cm[2 * k + 2].x);
-                    m.y = pk_max_u16(pk_max_u16(m.y, cm[2 * k + 1].y), cm[2 * k + 2].y);
-                    m.z = pk_max_u16(pk_max_u16(m.z, cm[2 * k + 1].z), cm[2 * k + 2].z);
-                    m.w = pk_max_u16(pk_max_u16(m.w, cm[2 * k + 1].w), cm[2 * k + 2].w);
-                    *(uint4*)(y + (((int64_t)n * Hp + ph) * Wp + pw) * 64 + cg * 8) = m;
-                }
-            }
-            continue;
-        }
-        for (int i = tid; i < R * SP_PW * 8; i += 256) {
-            const int cg = i & 7, pix = i >> 3;
-            const int pr = pix / SP_PW, pc = pix - pr * SP_PW;
-            const int ph = ph0 + pr, pw = pw0 + pc;
-            if (ph >= Hp || pw >= Wp) continue;
-            // every stem value is a ReLU output (>= 0, possibly -0): with the sign bit cleared the
-            // bf16 bit patterns order like the values, so the max runs as packed u16 max
-            uint4 m = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-            for (int dr = 0; dr < 3; ++dr)
-#pragma unroll
-                for (int dc = 0; dc < 3; ++dc) {
-                    const uint4 v = *(const uint4*)(S + ((2 * pr + dr) * SP_SC + 2 * pc + dc) * SP_SPITCH + cg * 16);
-                    m.x = pk_max_u16(m.x, v.x & 0x7fff7fffu);
-                    m.y = pk_max_u16(m.y, v.y & 0x7fff7fffu);
-                    m.z = pk_max_u16(m.z, v.z & 0x7fff7fffu);
-                    m.w = pk_max_u16(m.w, v.w & 0x7fff7fffu);
-                }
-            *(uint4*)(y + (((int64_t)n * Hp + ph) * Wp + pw) * 64 + cg * 8) = m;
-        }
+        if constexpr (V2)
+            stem_pool_pairs(S, y, n, ph0, pw0, R, SR, Hp, Wp);
+        else
+            stem_pool_masked(S, y, n, ph0, pw0, R, Hp, Wp);
     }
 }
 
@@ -651,14 +690,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_v3_kernel(const bf16* __rest
     const int ntiles = N * nct;
     const int fr = lane & 15, fq = lane >> 4;
     bf16x8 wv[7][4];
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) wv[kh][jn] = *(const bf16x8*)(w + (jn * 16 + fr) * 224 + kh * 32 + fq * 8);
     f32x4 bv[4];
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn) bv[jn] = *(const f32x4*)(bias + jn * 16 + fq * 4);
-    __builtin_amdgcn_s_waitcnt(0);   // weights / bias retired before the tile loop (see stem_pool_kernel)
+    stem_load_weights(w, bias, fr, fq, wv, bv);
 
     // patch pixel j of this thread (i = 256 j + tid): row i / SP_IC (input row - 5), column (c0 + 16 j) mod SP_IC
     // (256 = 10 x 24 + 16); offset in elements from the tile's pixel (0, ic0); p_ok bit j: in the patch, row in image
@@ -732,37 +765,15 @@ __global__ __launch_bounds__(256, 2) void stem_pool_v3_kernel(const bf16* __rest
             const int pp = f * 16 + fr;
             const char* xa = In + ((2 * min(sr, SR - 1)) * SP_IC + 2 * sc + 2 * fq) * 8;
             f32x4 acc[4];
-#pragma unroll
-            for (int jn = 0; jn < 4; ++jn) acc[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kh = 0; kh < 7; ++kh) {
-                const bf16x8 xv = *(const bf16x8*)(xa + kh * SP_IC * 8);
-#pragma unroll
-                for (int jn = 0; jn < 4; ++jn)
-                    acc[jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv[kh][jn], xv, acc[jn], 0, 0, 0);
-            }
-            // bias + ReLU on the rounded bf16 pairs (V2's epilogue), 0 outside the stem image
+            stem_frag_mma(xa, wv, acc);
+            // V2's epilogue, 0 outside the stem image
             bool ok = pp < P;
             if (cedge || ((rowmask_frags >> q) & 1u)) {
                 const int gr = sr - 1, gc = sc0 + sc;
                 ok = ok && gr >= 0 && gr < Hs && gc >= 0 && gc < Ws;
             }
             if (ok) {
-                char* sw = S + pp * SP_SPITCH + fq * 8;
-#pragma unroll
-                for (int jn = 0; jn < 4; ++jn) {
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-                    typedef short s16x2 __attribute__((ext_vector_type(2)));
-                    uint32_t o[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        s16x2 v = __builtin_bit_cast(s16x2, __builtin_convertvector(
-                            (f32x2{acc[jn][2 * h] + bv[jn][2 * h], acc[jn][2 * h + 1] + bv[jn][2 * h + 1]}), bf16x2));
-                        o[h] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(v, s16x2{0, 0}));
-                    }
-                    *(uint2*)(sw + jn * 32) = make_uint2(o[0], o[1]);
-                }
+                stem_relu_pack(acc, bv, S + pp * SP_SPITCH + fq * 8, true);
             } else if (pp < P) {
                 char* sw = S + pp * SP_SPITCH + fq * 8;
 #pragma unroll
@@ -775,42 +786,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_v3_kernel(const bf16* __rest
             }
         }
         __syncthreads();
-        // V2's pool: item = (pooled row pair, column, 8-channel group), stem rows 4 pr2 .. + 4
-        const int NR2 = (R + 1) / 2;
-        for (int i = tid; i < NR2 * SP_PW * 8; i += 256) {
-            const int cg = i & 7, pix = i >> 3;
-            const int pr2 = pix / SP_PW, pc = pix - pr2 * SP_PW;
-            const int pw = pw0 + pc;
-            if (pw >= Wp) continue;
-            uint4 cm[5];
-#pragma unroll
-            for (int dr = 0; dr < 5; ++dr) {
-                const int srr = 4 * pr2 + dr;
-                uint4 m = make_uint4(0u, 0u, 0u, 0u);
-                if (srr < SR) {
-#pragma unroll
-                    for (int dc = 0; dc < 3; ++dc) {
-                        const uint4 v = *(const uint4*)(S + (srr * SP_SC + 2 * pc + dc) * SP_SPITCH + cg * 16);
-                        m.x = pk_max_u16(m.x, v.x);
-                        m.y = pk_max_u16(m.y, v.y);
-                        m.z = pk_max_u16(m.z, v.z);
-                        m.w = pk_max_u16(m.w, v.w);
-                    }
-                }
-                cm[dr] = m;
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int pr = 2 * pr2 + k, ph = pr;
-                if (pr >= R || ph >= Hp) break;
-                uint4 m = cm[2 * k];
-                m.x = pk_max_u16(pk_max_u16(m.x, cm[2 * k + 1].x), cm[2 * k + 2].x);
-                m.y = pk_max_u16(pk_max_u16(m.y, cm[2 * k + 1].y), cm[2 * k + 2].y);
-                m.z = pk_max_u16(pk_max_u16(m.z, cm[2 * k + 1].z), cm[2 * k + 2].z);
-                m.w = pk_max_u16(pk_max_u16(m.w, cm[2 * k + 1].w), cm[2 * k + 2].w);
-                *(uint4*)(y + (((int64_t)n * Hp + ph) * Wp + pw) * 64 + cg * 8) = m;
-            }
-        }
+        stem_pool_pairs(S, y, n, 0, pw0, R, SR, Hp, Wp);   // one row tile: ph0 = 0
     }
 }
 
@@ -856,18 +832,9 @@ __global__ __launch_bounds__(256, 1) void stem16_pool_kernel(const bf16* __restr
         *(bf16x8*)(Wl + co * S16_WPITCH + c * 16) = *(const bf16x8*)(w + co * 896 + c * 8);
     }
     f32x4 bv[4];
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn) bv[jn] = *(const f32x4*)(bias + jn * 16 + fq * 4);
-    __builtin_amdgcn_s_waitcnt(0);   // bias retired before the loop (see stem_pool_kernel)
+    stem_load_bias(bias, fq, bv);
 
-    auto tile_origin = [&](int t, int& n, int& ph0, int& pw0) {
-        t = xcd_remap(t, ntiles);
-        n = t / (nrt * nct);
-        const int rem = t - n * (nrt * nct);
-        const int rt = rem / nct;
-        ph0 = rt * R;
-        pw0 = (rem - rt * nct) * SP_PW;
-    };
+    auto tile_origin = [&](int t, int& n, int& ph0, int& pw0) { sp_tile_origin(t, ntiles, nrt, nct, R, n, ph0, pw0); };
     uint4 pv[S16_LOADS];
     auto load_patch = [&](int t) {
         int n, ph0, pw0;
@@ -979,24 +946,7 @@ __global__ __launch_bounds__(256, 1) void stem16_pool_kernel(const bf16* __restr
             __syncthreads();
             continue;
         }
-        for (int i = tid; i < R * SP_PW * 8; i += 256) {
-            const int cg = i & 7, pix = i >> 3;
-            const int pr = pix / SP_PW, pc = pix - pr * SP_PW;
-            const int ph = ph0 + pr, pw = pw0 + pc;
-            if (ph >= Hp || pw >= Wp) continue;
-            uint4 m = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-            for (int dr = 0; dr < 3; ++dr)
-#pragma unroll
-                for (int dc = 0; dc < 3; ++dc) {
-                    const uint4 v = *(const uint4*)(S + ((2 * pr + dr) * SP_SC + 2 * pc + dc) * SP_SPITCH + cg * 16);
-                    m.x = pk_max_u16(m.x, v.x & 0x7fff7fffu);
-                    m.y = pk_max_u16(m.y, v.y & 0x7fff7fffu);
-                    m.z = pk_max_u16(m.z, v.z & 0x7fff7fffu);
-                    m.w = pk_max_u16(m.w, v.w & 0x7fff7fffu);
-                }
-            *(uint4*)(y + (((int64_t)n * Hp + ph) * Wp + pw) * 64 + cg * 8) = m;
-        }
+        stem_pool_masked(S, y, n, ph0, pw0, R, Hp, Wp);
         __syncthreads();   // S and In are rewritten by the next tile
     }
 }
@@ -1515,56 +1465,61 @@ hipError_t cbw_stem_conv(const uint16_t* x, const uint16_t* w, const float* bias
     return hipGetLastError();
 }
 
+// The fused stem kernels' tile plan: Hp pooled rows in nrt row tiles of R <= rmax rows, Wp pooled columns in nct
+// column tiles of SP_PW, one tile per (pair, row tile, column tile); a persistent grid of at most grid_cap blocks.
+// grid == 0: the tile count does not fit an int.
+struct StemTilePlan {
+    int nrt, R, nct;
+    unsigned grid;
+};
+static StemTilePlan stem_tile_plan(int N, int Hp, int Wp, int rmax, int64_t grid_cap) {
+    StemTilePlan p;
+    p.nrt = (Hp + rmax - 1) / rmax;
+    p.R = (Hp + p.nrt - 1) / p.nrt;
+    p.nct = (Wp + SP_PW - 1) / SP_PW;
+    const int64_t nt = (int64_t)N * p.nrt * p.nct;
+    p.grid = nt >= (1LL << 31) ? 0u : (unsigned)std::min<int64_t>(nt, grid_cap);
+    return p;
+}
+
 hipError_t cbw_stem_pool(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y, int N, int H, int W,
                          int Hs, int Ws, int Hp, int Wp, hipStream_t st) {
     if (N <= 0 || Hp <= 0 || Wp <= 0) return hipSuccess;
-    const int nrt = (Hp + SP_RMAX - 1) / SP_RMAX;
-    const int R = (Hp + nrt - 1) / nrt;
-    const int nct = (Wp + SP_PW - 1) / SP_PW;
-    const int64_t nt = (int64_t)N * nrt * nct;
-    if (nt >= (1LL << 31)) return hipErrorInvalidValue;
-    const int64_t G = std::min<int64_t>(nt, 2 * (int64_t)cbw_num_cus());
+    const StemTilePlan p = stem_tile_plan(N, Hp, Wp, SP_RMAX, 2 * (int64_t)cbw_num_cus());
+    if (!p.grid) return hipErrorInvalidValue;
     const char* v1 = getenv("CBW_STEM_V1");   // A/B: the round-4 epilogue and pool (read per call)
     // round 6's V3 (default on full-height tiles; CBW_STEM_V3=0: V2): tools/stem_bench.py, 625 LEF pairs, alternating
     // runs 361.9 / 367.5 vs 373.2 / 377.3 us, bit-identical
     const char* v3 = getenv("CBW_STEM_V3");
-    if (nrt == 1 && (!v3 || atoi(v3) != 0) && !(v1 && atoi(v1) == 1))
-        hipLaunchKernelGGL(stem_pool_v3_kernel, dim3((unsigned)G), dim3(256), sp_lds_bytes(R), st, (const bf16*)x,
-                           (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nct);
+    if (p.nrt == 1 && (!v3 || atoi(v3) != 0) && !(v1 && atoi(v1) == 1))
+        hipLaunchKernelGGL(stem_pool_v3_kernel, dim3(p.grid), dim3(256), sp_lds_bytes(p.R), st, (const bf16*)x,
+                           (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, p.R, p.nct);
     else if (v1 && atoi(v1) == 1)
-        hipLaunchKernelGGL(stem_pool_kernel<false>, dim3((unsigned)G), dim3(256), sp_lds_bytes(R), st, (const bf16*)x,
-                           (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nrt, nct);
+        hipLaunchKernelGGL(stem_pool_kernel<false>, dim3(p.grid), dim3(256), sp_lds_bytes(p.R), st, (const bf16*)x,
+                           (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, p.R, p.nrt, p.nct);
     else
-        hipLaunchKernelGGL(stem_pool_kernel<true>, dim3((unsigned)G), dim3(256), sp_lds_bytes(R), st, (const bf16*)x,
-                           (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nrt, nct);
+        hipLaunchKernelGGL(stem_pool_kernel<true>, dim3(p.grid), dim3(256), sp_lds_bytes(p.R), st, (const bf16*)x,
+                           (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, p.R, p.nrt, p.nct);
     return hipGetLastError();
 }
 
 hipError_t cbw_stem16_pool(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y, int N, int H,
                            int W, int Hs, int Ws, int Hp, int Wp, hipStream_t st) {
     if (N <= 0 || Hp <= 0 || Wp <= 0) return hipSuccess;
-    const int nrt = (Hp + S16_RMAX - 1) / S16_RMAX;
-    const int R = (Hp + nrt - 1) / nrt;
-    const int nct = (Wp + SP_PW - 1) / SP_PW;
-    const int64_t nt = (int64_t)N * nrt * nct;
-    if (nt >= (1LL << 31)) return hipErrorInvalidValue;
-    const int64_t G = std::min<int64_t>(nt, cbw_num_cus());
-    hipLaunchKernelGGL(stem16_pool_kernel<false>, dim3((unsigned)G), dim3(256), s16_lds_bytes(R), st, (const bf16*)x,
-                       (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nrt, nct);
+    const StemTilePlan p = stem_tile_plan(N, Hp, Wp, S16_RMAX, cbw_num_cus());
+    if (!p.grid) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stem16_pool_kernel<false>, dim3(p.grid), dim3(256), s16_lds_bytes(p.R), st, (const bf16*)x,
+                       (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, p.R, p.nrt, p.nct);
     return hipGetLastError();
 }
 
 hipError_t cbw_stem16_pool_x3(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y, int N, int H,
                               int W, int Hs, int Ws, int Hp, int Wp, hipStream_t st) {
     if (N <= 0 || Hp <= 0 || Wp <= 0) return hipSuccess;
-    const int nrt = (Hp + S16_RMAX_X3 - 1) / S16_RMAX_X3;
-    const int R = (Hp + nrt - 1) / nrt;
-    const int nct = (Wp + SP_PW - 1) / SP_PW;
-    const int64_t nt = (int64_t)N * nrt * nct;
-    if (nt >= (1LL << 31)) return hipErrorInvalidValue;
-    const int64_t G = std::min<int64_t>(nt, cbw_num_cus());
-    hipLaunchKernelGGL(stem16_pool_kernel<true>, dim3((unsigned)G), dim3(256), s16_lds_bytes(R, true), st,
-                       (const bf16*)x, (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, R, nrt, nct);
+    const StemTilePlan p = stem_tile_plan(N, Hp, Wp, S16_RMAX_X3, cbw_num_cus());
+    if (!p.grid) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stem16_pool_kernel<true>, dim3(p.grid), dim3(256), s16_lds_bytes(p.R, true), st,
+                       (const bf16*)x, (const bf16*)w, bias, (bf16*)y, N, H, W, Hs, Ws, Hp, Wp, p.R, p.nrt, p.nct);
     return hipGetLastError();
 }
 

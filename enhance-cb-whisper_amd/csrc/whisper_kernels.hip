@@ -339,96 +339,19 @@ __global__ void dec_kv_append_kernel(const bf16* __restrict__ qkv, bf16* __restr
     }
 }
 
-// one query row per (row, head) against n_keys cached keys (decode step); q pre-scaled.
-// K/V element (key j, dim c) of kv batch b at kv + b*kv_bstride + j*D + c; row r reads kv batch r / rows_per_kv.
-constexpr int DA_MAXK = 1536;
-__global__ __launch_bounds__(256) void dec_attention_kernel(const bf16* __restrict__ q, int ldq,
-                                                            const bf16* __restrict__ kc, const bf16* __restrict__ vc,
-                                                            int64_t kv_bstride, int n_keys_all, int rows_per_kv,
-                                                            bf16* __restrict__ out, int D, int causal) {
-    __shared__ float qs[64];
-    __shared__ float ps[DA_MAXK];
-    __shared__ float red[8];
-    __shared__ float pv[32][65];
-    const int r = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-    const int b = r / rows_per_kv;
-    // causal (prefill): query row r is prefix token r and sees keys 0..r
-    const int n_keys = causal ? min(n_keys_all, r + 1) : n_keys_all;
-    if (tid < 64) qs[tid] = bf2f(q[(int64_t)r * ldq + h * 64 + tid]);
-    __syncthreads();
-    const bf16* kb = kc + b * kv_bstride + h * 64;
-    const bf16* vb = vc + b * kv_bstride + h * 64;
-    float mx = -INFINITY;
-    for (int j = tid; j < n_keys; j += 256) {
-        const bf16* kr = kb + (int64_t)j * D;
-        float s = 0.f;
+// fma8: acc[e] += p * v[e] over the 8 dims of one 16-byte V load (the P.V accumulate of the decode-attention kernels)
+CBW_DEV void fma8(float p, bf16x8 v, float (&acc)[8]) {
 #pragma unroll
-        for (int c = 0; c < 64; c += 8) {
-            const bf16x8 kv = *(const bf16x8*)(kr + c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s = fmaf(qs[c + e], bf2f(kv[e]), s);
-        }
-        ps[j] = s;
-        mx = fmaxf(mx, s);
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int j = tid; j < n_keys; j += 256) {
-        const float e = __expf(ps[j] - mx);
-        ps[j] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) red[4 + (tid >> 6)] = sum;
-    __syncthreads();
-    const float inv = 1.0f / (red[4] + red[5] + red[6] + red[7]);
-    // P.V: thread = 8 dims (one 16-byte load per key) x every 32nd key, four keys in flight per step;
-    // the 32 key groups meet in LDS (fixed order)
-    const int dg = tid & 7, kg = tid >> 3;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const bf16* vd = vb + dg * 8;
-    int j = kg;
-    for (; j + 96 < n_keys; j += 128) {
-        bf16x8 v4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v4[u] = *(const bf16x8*)(vd + (int64_t)(j + 32 * u) * D);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float p = ps[j + 32 * u];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, bf2f(v4[u][e]), acc[e]);
-        }
-    }
-    for (; j < n_keys; j += 32) {
-        const bf16x8 vv = *(const bf16x8*)(vd + (int64_t)j * D);
-        const float p = ps[j];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, bf2f(vv[e]), acc[e]);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) pv[kg][dg * 8 + e] = acc[e];
-    __syncthreads();
-    if (tid < 64) {
-        float o = 0.f;
-        for (int k = 0; k < 32; ++k) o += pv[k][tid];
-        out[(int64_t)r * D + h * 64 + tid] = f2bf(o * inv);
-    }
+    for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, bf2f(v[e]), acc[e]);
 }
 
-// Cross-attention probabilities of one head (token-level timestamps: the alignment heads' weights that
-// transformers' _extract_token_timestamps reads from generate's cross_attentions): row r = softmax_j(q_r . k_j)
-// over the n_keys encoder frames, the same scores, max and exponentials as dec_attention_kernel; out f32 [T][n_keys].
-__global__ __launch_bounds__(256) void dec_cross_probs_kernel(const bf16* __restrict__ q, int ldq,
-                                                              const bf16* __restrict__ kc, int n_keys, int D, int h,
-                                                              float* __restrict__ out) {
-    __shared__ float qs[64];
-    __shared__ float ps[DA_MAXK];
-    __shared__ float red[8];
-    const int r = blockIdx.x, tid = threadIdx.x;
+// dec_row_softmax: the softmax statistics of query row r, head h against n_keys keys (key j's 64 dims of the head at
+// kc + j * D + h * 64), by a block of 256 threads.  The query is staged into qs[64], thread t scores keys t, t + 256, ... (one fmaf chain
+// over the 64 dims), the block max meets in red[0..3] and the block sum in red[4..7].  Leaves the unnormalised
+// exponentials in ps[0..n_keys) and returns 1 / sum; ps[] is visible to the whole block on return.
+CBW_DEV float dec_row_softmax(const bf16* q, int ldq, int r, int h, const bf16* kc, int n_keys, int D, float* qs,
+                              float* ps, float* red) {
+    const int tid = threadIdx.x;
     if (tid < 64) qs[tid] = bf2f(q[(int64_t)r * ldq + h * 64 + tid]);
     __syncthreads();
     const bf16* kb = kc + h * 64;
@@ -459,7 +382,65 @@ __global__ __launch_bounds__(256) void dec_cross_probs_kernel(const bf16* __rest
     sum = wave_sum(sum);
     if ((tid & 63) == 0) red[4 + (tid >> 6)] = sum;
     __syncthreads();
-    const float inv = 1.0f / (red[4] + red[5] + red[6] + red[7]);
+    return 1.0f / (red[4] + red[5] + red[6] + red[7]);
+}
+
+// one query row per (row, head) against n_keys cached keys (decode step); q pre-scaled.
+// K/V element (key j, dim c) of kv batch b at kv + b*kv_bstride + j*D + c; row r reads kv batch r / rows_per_kv.
+constexpr int DA_MAXK = 1536;
+__global__ __launch_bounds__(256) void dec_attention_kernel(const bf16* __restrict__ q, int ldq,
+                                                            const bf16* __restrict__ kc, const bf16* __restrict__ vc,
+                                                            int64_t kv_bstride, int n_keys_all, int rows_per_kv,
+                                                            bf16* __restrict__ out, int D, int causal) {
+    __shared__ float qs[64];
+    __shared__ float ps[DA_MAXK];
+    __shared__ float red[8];
+    __shared__ float pv[32][65];
+    const int r = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    const int b = r / rows_per_kv;
+    // causal (prefill): query row r is prefix token r and sees keys 0..r
+    const int n_keys = causal ? min(n_keys_all, r + 1) : n_keys_all;
+    const float inv = dec_row_softmax(q, ldq, r, h, kc + b * kv_bstride, n_keys, D, qs, ps, red);
+    const bf16* vb = vc + b * kv_bstride + h * 64;
+    // P.V: thread = 8 dims (one 16-byte load per key) x every 32nd key, four keys in flight per step;
+    // the 32 key groups meet in LDS (fixed order)
+    const int dg = tid & 7, kg = tid >> 3;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bf16* vd = vb + dg * 8;
+    int j = kg;
+    for (; j + 96 < n_keys; j += 128) {
+        bf16x8 v4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v4[u] = *(const bf16x8*)(vd + (int64_t)(j + 32 * u) * D);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) fma8(ps[j + 32 * u], v4[u], acc);
+    }
+    for (; j < n_keys; j += 32) {
+        const bf16x8 vv = *(const bf16x8*)(vd + (int64_t)j * D);
+        fma8(ps[j], vv, acc);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pv[kg][dg * 8 + e] = acc[e];
+    __syncthreads();
+    if (tid < 64) {
+        float o = 0.f;
+        for (int k = 0; k < 32; ++k) o += pv[k][tid];
+        out[(int64_t)r * D + h * 64 + tid] = f2bf(o * inv);
+    }
+}
+
+// Cross-attention probabilities of one head (token-level timestamps: the alignment heads' weights that
+// transformers' _extract_token_timestamps reads from generate's cross_attentions): row r = softmax_j(q_r . k_j)
+// over the n_keys encoder frames, dec_attention_kernel's scores, max and exponentials (dec_row_softmax); out f32
+// [T][n_keys].
+__global__ __launch_bounds__(256) void dec_cross_probs_kernel(const bf16* __restrict__ q, int ldq,
+                                                              const bf16* __restrict__ kc, int n_keys, int D, int h,
+                                                              float* __restrict__ out) {
+    __shared__ float qs[64];
+    __shared__ float ps[DA_MAXK];
+    __shared__ float red[8];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float inv = dec_row_softmax(q, ldq, r, h, kc, n_keys, D, qs, ps, red);
     for (int j = tid; j < n_keys; j += 256) out[(int64_t)r * n_keys + j] = ps[j] * inv;
 }
 
@@ -636,6 +617,24 @@ __device__ __forceinline__ uint32_t dtw_block16(const float (&mv)[16], int b, in
 constexpr int DS_CHUNK = 64;
 constexpr int DS_MAXS = 24;   // 1536 keys
 
+// dot16_quad: q . k over the 64 dims of a head by the four lanes of a key, 16 dims each: the lane's two 8-dim halves
+// in one fmaf chain (a[0], b[0], a[1], b[1], ...), then the four lanes' sums by two lane exchanges; every lane of the
+// four returns the dot product.  The query halves are floats in LDS (split kernel) or bf16 in registers (self kernel).
+CBW_DEV float dot16_elem(float v) { return v; }
+CBW_DEV float dot16_elem(bf16 v) { return bf2f(v); }
+template <class Q>
+CBW_DEV float dot16_quad(const Q& qa, const Q& qb, bf16x8 ka, bf16x8 kb) {
+    float d = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        d = fmaf(dot16_elem(qa[e]), bf2f(ka[e]), d);
+        d = fmaf(dot16_elem(qb[e]), bf2f(kb[e]), d);
+    }
+    d += xor_lane<1>(d);
+    d += xor_lane<2>(d);
+    return d;
+}
+
 template <int RMAX>
 __global__ __launch_bounds__(256) void dec_attn_split_kernel(const bf16* __restrict__ q, int ldq,
                                                              const bf16* __restrict__ kc, const bf16* __restrict__ vc,
@@ -684,14 +683,7 @@ __global__ __launch_bounds__(256) void dec_attn_split_kernel(const bf16* __restr
 #pragma unroll
         for (int i = 0; i < RMAX; ++i) {
             if (i < R) {
-                float d = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    d = fmaf(qs[i][p * 16 + e], bf2f(k0[e]), d);
-                    d = fmaf(qs[i][p * 16 + 8 + e], bf2f(k1[e]), d);
-                }
-                d += xor_lane<1>(d);
-                d += xor_lane<2>(d);
+                const float d = dot16_quad(qs[i] + p * 16, qs[i] + p * 16 + 8, k0, k1);
                 if (p == 0) ps[i][j] = j < nk ? d : -INFINITY;
             }
         }
@@ -720,6 +712,8 @@ __global__ __launch_bounds__(256) void dec_attn_split_kernel(const bf16* __restr
 #pragma unroll
         for (int i = 0; i < RMAX; ++i)
             if (i < R) {
+                // not fma8: through the helper the RMAX = 8 kernel's conversions are vectorised and its registers and
+                // occupancy change (84 -> 79 VGPRs, 5 -> 6 waves per SIMD)
                 const float pr = ps[i][jj];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[i][e] = fmaf(pr, bf2f(v[e]), acc[i][e]);
@@ -821,14 +815,7 @@ __device__ __forceinline__ void dec_self_attn_body(const bf16* __restrict__ qr, 
     float mx = -INFINITY;
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
-        float d = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            d = fmaf(bf2f(qa[e]), bf2f(ka[u][e]), d);
-            d = fmaf(bf2f(qb[e]), bf2f(kb2[u][e]), d);
-        }
-        d += xor_lane<1>(d);
-        d += xor_lane<2>(d);
+        const float d = dot16_quad(qa, qb, ka[u], kb2[u]);
         sc[u] = j + 64 * u < nk ? d : -INFINITY;
         mx = fmaxf(mx, sc[u]);
     }
@@ -847,11 +834,7 @@ __device__ __forceinline__ void dec_self_attn_body(const bf16* __restrict__ qr, 
     __syncthreads();
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int u = 0; u < 2 * NP; ++u) {
-        const float pr = ps[kg + 32 * u];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(pr, bf2f(vv[u][e]), acc[e]);
-    }
+    for (int u = 0; u < 2 * NP; ++u) fma8(ps[kg + 32 * u], vv[u], acc);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {   // the wave's 8 key groups (lane bits 3-5), then the 4 waves in LDS
         float a = acc[e];
