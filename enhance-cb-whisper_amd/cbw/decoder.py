@@ -391,7 +391,8 @@ class DecoderEngine:
     def greedy_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], eos: int, max_lengths,
                        bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules=None,
                        check_every: int = 8, return_logprobs: bool = False, max_slots: Optional[int] = None,
-                       max_rows: int = 16) -> List:
+                       max_rows: int = 16, repetition_penalty: Optional[float] = None,
+                       no_repeat_ngram_size: int = 0) -> List:
         """Greedy search (HF 4.37.2 greedy branch of GenerationMixin.generate, the call of pba_whisper.py:318-331 and
         :425-442 with num_beams = 1, do_sample = False) for several windows in lock step with no host round trip per
         token: windows = [(enc_out f32 [1500, D] post-LN, decoder prefix)], max_lengths one per window (or one int),
@@ -404,24 +405,42 @@ class DecoderEngine:
         back in one copy and cbw.generate.greedy_replay reads them: finished windows leave, pending ones take their
         slots; steps enqueued past a row's end are ignored (cbw_greedy_select's invariant keeps them inside the
         cache).  Begin suppression and the rules' begin index are len(prefix); no forced positions.
+        ``repetition_penalty`` / ``no_repeat_ngram_size``: the caller's two history processors in front of the choice
+        (cbw_history_rules, see _lock_step); unset, nothing is allocated or launched for them.
         Returns the sequences (prefix included) in window order; with ``return_logprobs`` (sequence, per-step
         log-probs) pairs."""
         def select(args, live, r0, stream):
             _lib.check(self.lib.cbw_greedy_select(*args, stream), "cbw_greedy_select")
         return self._lock_step("greedy_windows", windows, eos, max_lengths, bias, bias_begin, rules, select,
-                               check_every, return_logprobs, max_slots, max_rows=max_rows)
+                               check_every, return_logprobs, max_slots, max_rows=max_rows,
+                               repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
     def _lock_step(self, name: str, windows, eos: int, max_lengths, bias, bias_begin, rules, select: callable,
                    check_every: int, return_logprobs: bool, max_slots: Optional[int], replayed: Optional[callable] = None,
-                   max_rows: int = 16) -> List:
+                   max_rows: int = 16, repetition_penalty: Optional[float] = None,
+                   no_repeat_ngram_size: int = 0) -> List:
         """The lock-step driver greedy_windows and sample_windows share: slot admission, the device log of
         ``check_every`` steps, the one copy per replay, cbw.generate.greedy_replay and the divergence check.  Per step
         and slice of 16 rows starting at ``r0`` (those kernels take at most 16; every argument is row-indexed)
         ``select(args, live, r0, stream)`` makes the rows' choice: ``args`` are the arguments cbw_greedy_select and
         cbw_sample_select have in common (logits ... logprob, writing the step's row of the log), ``live[slot]`` the
         window in each slot (None: empty).  ``replayed(window, taken, finished)`` is called after every replay with the
-        number of logged steps the window took from it."""
+        number of logged steps the window took from it.
+        With ``repetition_penalty`` (not None and != 1) or ``no_repeat_ngram_size`` > 0, HF 4.37.2's
+        RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor run on the slice's logits in front of
+        ``select`` (cbw_history_rules, one launch per step and slice) from a token history per slot on the device:
+        ``hist`` int32 [slots, max_len + 1] and ``hist_len`` [slots], the prefix written on admission, every later token
+        appended by the kernel itself from the previous step's token row of the log (the previous replay batch's last
+        row for a batch's first step; none at the very first step).  The kernel appends only where hist_len == the
+        position of the row's last token, so a reused slot, whose fresh history is one longer than that, takes
+        nothing from the token row its previous window left.  Neither control set: nothing is allocated or launched
+        for them."""
         from .generate import greedy_replay
+        penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        ngram = int(no_repeat_ngram_size or 0)
+        if not (penalty > 0 and math.isfinite(penalty)) or ngram < 0:
+            raise ValueError(f"{name} needs a finite repetition_penalty > 0 and no_repeat_ngram_size >= 0")
+        history = penalty != 1.0 or ngram > 0
         n = len(windows)
         limits = [int(max_lengths)] * n if isinstance(max_lengths, int) else [int(m) for m in max_lengths]
         if len(limits) != n:
@@ -453,6 +472,11 @@ class DecoderEngine:
             # the log: per step one row of {tokens, log-probs (f32 bits), active} x slots, so a replay is one copy
             log = torch.zeros((check_every, 3, slots), dtype=torch.int32, device=dev)
             log_lp = log.view(torch.float32)
+            if history:
+                hist = torch.zeros((slots, self.max_len + 1), dtype=torch.int32, device=dev)
+                hist_len = torch.zeros((slots,), dtype=torch.int32, device=dev)
+                last_pos = torch.zeros((slots,), dtype=torch.int32, device=dev)   # self._posr - 1: the last tokens'
+                last_tok = 0   # the previous step's token row of the log (0: none yet)
             live: List[Optional[int]] = [None] * slots   # the window in each slot
             seqs: List[Optional[List[int]]] = [None] * slots
             lps: List[List[float]] = [[] for _ in range(slots)]
@@ -466,6 +490,9 @@ class DecoderEngine:
                         ts_state[slot] = torch.tensor([0, -1, -1, -1], dtype=torch.int32)
                         limit[slot:slot + 1].fill_(limits[i])
                         active[slot:slot + 1].fill_(1)
+                        if history:
+                            hist[slot, :len(prefix)] = torch.tensor(list(prefix), dtype=torch.int32)
+                            hist_len[slot:slot + 1].fill_(len(prefix))
                         live[slot], seqs[slot], lps[slot] = i, list(prefix), []
                 # no row needs more steps than the longest remainder; the step after the last of those is not run
                 left = max(limits[w] - len(seqs[s]) for s, w in enumerate(live) if w is not None)
@@ -473,12 +500,21 @@ class DecoderEngine:
                 lg, tsp, posp, limp, actp = (t.data_ptr() for t in (self._logits, ts_state, self._posr, limit, active))
                 for c in range(steps):
                     tokp, lpp = log[c, 0].data_ptr(), log_lp[c, 1].data_ptr()
+                    if history:
+                        torch.sub(self._posr, 1, out=last_pos)
                     for r0 in range(0, slots, 16):
                         o = 4 * r0   # int32 / f32 rows
+                        if history:
+                            _lib.check(self.lib.cbw_history_rules(
+                                lg + o * self.vpad, min(16, slots - r0), self.vocab, self.vpad,
+                                hist.data_ptr() + o * hist.shape[1], hist.shape[1], hist_len.data_ptr() + o,
+                                last_tok + o if last_tok else None, last_pos.data_ptr() + o, actp + o, penalty, ngram,
+                                stream), "cbw_history_rules")
                         select((lg + o * self.vpad, min(16, slots - r0), self.vocab, self.vpad, _lib.ptr(bias),
                                 _lib.ptr(bias_begin), tb, no_ts, eos, max_initial, tsp + 4 * o, posp + o, limp + o,
                                 actp + o, tokp + o, lpp + o), live, r0, stream)
                     log[c, 2].copy_(active)
+                    last_tok = tokp
                     if c + 1 == left:
                         break
                     self.step_rows(log[c, 0])
@@ -503,16 +539,19 @@ class DecoderEngine:
 
     def greedy_dev(self, enc_out: torch.Tensor, prefix: Sequence[int], eos: int, max_length: int,
                    bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules=None, check_every: int = 8,
-                   return_logprobs: bool = False):
+                   return_logprobs: bool = False, repetition_penalty: Optional[float] = None,
+                   no_repeat_ngram_size: int = 0):
         """greedy_windows over one window: enc_out f32 [1500, D] (or [1, 1500, D]) -> the sequence, or with
         ``return_logprobs`` (sequence, per-step log-probs)."""
         return self.greedy_windows([(enc_out, prefix)], eos, [max_length], bias, bias_begin, rules, check_every,
-                                   return_logprobs)[0]
+                                   return_logprobs, repetition_penalty=repetition_penalty,
+                                   no_repeat_ngram_size=no_repeat_ngram_size)[0]
 
     def sample_windows(self, windows: Sequence[Tuple[torch.Tensor, Sequence[int]]], eos: int, max_lengths,
                        bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules, temperature: float,
                        generators, top_k: int = 50, check_every: int = 8, max_slots: Optional[int] = None,
-                       max_rows: int = 16) -> List:
+                       max_rows: int = 16, repetition_penalty: Optional[float] = None,
+                       no_repeat_ngram_size: int = 0) -> List:
         """Temperature sampling (HF 4.37.2 sample branch of GenerationMixin.generate: the call of
         pba_whisper.py:318-331 with do_sample = True, and every temperature > 0 rung of generate_with_fallback,
         :425-442) for several windows in lock step with no host round trip per token: greedy_windows' driver with
@@ -525,6 +564,8 @@ class DecoderEngine:
         ``generators``: one device torch.Generator per window (a single one for a single window), each used by no
         other window.  Steps enqueued past a window's end consume draws; after the replay that ends a window its
         generator is set back to the state right after the draw of its last token, where sample_search leaves it.
+        ``repetition_penalty`` / ``no_repeat_ngram_size``: as greedy_windows (the processors act on the raw logits,
+        before the warpers).
         Returns (sequence incl. the prefix, per-step log-probs) per window, as sample_search."""
         if not (temperature > 0 and math.isfinite(temperature)) or top_k < 1:
             raise ValueError("sample_windows needs a finite temperature > 0 and top_k >= 1")
@@ -551,14 +592,17 @@ class DecoderEngine:
                 gens[w].set_state(states[w][taken - 1])
             states[w].clear()
         return self._lock_step("sample_windows", windows, eos, max_lengths, bias, bias_begin, rules, select,
-                               check_every, True, max_slots, replayed, max_rows=max_rows)
+                               check_every, True, max_slots, replayed, max_rows=max_rows,
+                               repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
     def sample_dev(self, enc_out: torch.Tensor, prefix: Sequence[int], eos: int, max_length: int,
                    bias: Optional[torch.Tensor], bias_begin: Optional[torch.Tensor], rules, temperature: float,
-                   generator: torch.Generator, top_k: int = 50, check_every: int = 8):
+                   generator: torch.Generator, top_k: int = 50, check_every: int = 8,
+                   repetition_penalty: Optional[float] = None, no_repeat_ngram_size: int = 0):
         """sample_windows over one window -> (sequence, per-step log-probs)."""
         return self.sample_windows([(enc_out, prefix)], eos, [max_length], bias, bias_begin, rules, temperature,
-                                   [generator], top_k, check_every)[0]
+                                   [generator], top_k, check_every, repetition_penalty=repetition_penalty,
+                                   no_repeat_ngram_size=no_repeat_ngram_size)[0]
 
     def sample_search(self, prefix: Sequence[int], eos: int, max_length: int, bias_at: callable, rules=None,
                       begin_index: int = 0, temperature: float = 0.0, top_k: int = 50,

@@ -344,6 +344,13 @@ hipError_t cbw_sample_select_launch(const float* logits, int B, int V, int ld, c
                                     int* ts_state, const int* pos_rows, const int* limit, int* active, int* tokens,
                                     float* logprob, float temperature, int top_k, const float* noise,
                                     int64_t noise_ld, hipStream_t st);
+// the repetition penalty and the no-repeat n-gram bans on up to 16 rows' logits in place, from a per-row token history
+// the kernel keeps itself (hist int32 [B][hist_ld], hist_len [B]); hist_ld <= CBW_HISTORY_MAX_LD: a block stages its
+// row's history in LDS
+constexpr int CBW_HISTORY_MAX_LD = 2048;
+hipError_t cbw_history_rules_launch(float* logits, int B, int V, int ld, int* hist, int hist_ld, int* hist_len,
+                                    const int* last_tokens, const int* pos_rows, const int* active,
+                                    float repetition_penalty, int no_repeat_ngram_size, hipStream_t st);
 hipError_t cbw_logprob_topk_launch(const float* logits, int B, int V, int ld, const float* bias, int64_t bias_ld,
                                    int k, float* lp, int* idx, hipStream_t st);
 hipError_t cbw_timestamp_rules_launch(const float* logits, int B, int V, int ld, const float* bias, const int* state,

@@ -3445,6 +3445,19 @@ int cbw_sample_select(const float* logits, int B, int V, int ld, const float* bi
     return CBW_OK;
 }
 
+int cbw_history_rules(float* logits, int B, int V, int ld, int32_t* hist, int hist_ld, int32_t* hist_len,
+                      const int32_t* last_tokens, const int32_t* pos_rows, const int32_t* active,
+                      float repetition_penalty, int no_repeat_ngram_size, cbw_stream_t stream) {
+    if (!logits || !hist || !hist_len || !pos_rows || !active || B < 1 || B > 16 || V < 1 || ld < V || hist_ld < 1 ||
+        hist_ld > CBW_HISTORY_MAX_LD)
+        return fail(CBW_ERR_INVALID, "bad arguments (B in [1, 16], ld >= V >= 1, hist_ld in [1, 2048])");
+    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty) || no_repeat_ngram_size < 0)
+        return fail(CBW_ERR_INVALID, "bad arguments (repetition_penalty > 0 and finite, no_repeat_ngram_size >= 0)");
+    HIPCHK(cbw_history_rules_launch(logits, B, V, ld, hist, hist_ld, hist_len, last_tokens, pos_rows, active,
+                                    repetition_penalty, no_repeat_ngram_size, (hipStream_t)stream));
+    return CBW_OK;
+}
+
 // ------------------------------------------------------------------ building block
 }  // extern "C"
 namespace {

@@ -698,6 +698,64 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const float* __rest
     select_finish(row, r, tok, lp, ts_state, pos_rows, limit, active, tokens, logprob);
 }
 
+// ---------------------------------------------------------------- the processors that read a row's token history
+// RepetitionPenaltyLogitsProcessor then NoRepeatNGramLogitsProcessor (transformers 4.37.2 _get_logits_processor's first
+// two, on the raw logits of a greedy or sample step), in place, in front of greedy_select_kernel / sample_select_kernel,
+// whose bias and rules are the processors after them.  One block per row; the work is the row's history (at most
+// hist_ld <= CBW_HISTORY_MAX_LD tokens, staged in LDS clamped into [0, V)), not a pass over V.
+//   upkeep: len = hist_len[r], the row's last token at position pos_rows[r].  len == pos + 1: the history is whole (a
+//   slot just admitted, its prefix written by the caller).  len == pos: the row moved one position since the last call,
+//   last_tokens[r] is appended.  Anything else, or an append that cannot be made (no last_tokens, len == hist_ld): the
+//   row is left as it is -- no address is formed from a bad state.
+//   penalty (p != 1): x[t] = x[t] < 0 ? x[t] * p : x[t] / p once per distinct token t: every entry's value is gathered
+//   into LDS before any is scattered, so the entries of one token write equal values.
+//   bans (n > 0, len + 1 >= n): x[hist[i + n - 1]] = -inf for every i in [0, len - n] whose n - 1 tokens equal the last
+//   n - 1 (cbw.decoder.banned_ngram_tokens), behind a barrier: -inf wins over a penalised value.
+constexpr int HR_THREADS = 256;
+
+__global__ __launch_bounds__(HR_THREADS) void history_rules_kernel(float* __restrict__ logits, int V, int ld, int* hist,
+                                                                   int hist_ld, int* hist_len,
+                                                                   const int* __restrict__ last_tokens,
+                                                                   const int* __restrict__ pos_rows,
+                                                                   const int* __restrict__ active, float p, int n) {
+    __shared__ int h[CBW_HISTORY_MAX_LD];
+    __shared__ float hv[CBW_HISTORY_MAX_LD];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    // block-uniform exits, all before the first barrier and before hist_len[r] is written
+    if (!active[r] || hist_ld < 1 || hist_ld > CBW_HISTORY_MAX_LD) return;
+    const int len = hist_len[r], pos = pos_rows[r];
+    if (len < 0 || len > hist_ld) return;
+    const bool append = len == pos;
+    if (append ? (!last_tokens || len >= hist_ld) : len - 1 != pos) return;
+    int* hr = hist + (int64_t)r * hist_ld;
+    float* x = logits + (int64_t)r * ld;
+    const int last = append ? last_tokens[r] : 0;
+    const int L = len + (append ? 1 : 0);   // <= hist_ld
+    for (int i = tid; i < L; i += HR_THREADS) h[i] = min(max(i < len ? hr[i] : last, 0), V - 1);
+    __syncthreads();   // every thread has read hist_len[r]
+    if (append && tid == 0) {
+        hr[len] = last;
+        hist_len[r] = L;
+    }
+    if (p != 1.f) {
+        for (int i = tid; i < L; i += HR_THREADS) hv[i] = x[h[i]];
+        __syncthreads();
+        for (int i = tid; i < L; i += HR_THREADS) {
+            const float v = hv[i];
+            x[h[i]] = v < 0.f ? v * p : __fdiv_rn(v, p);   // round to nearest, as torch and numpy divide
+        }
+        __syncthreads();   // the penalised values are written before a ban overwrites one
+    }
+    if (n > 0 && L + 1 >= n) {
+        const int* tail = h + (L - n + 1);   // the last n - 1 tokens
+        for (int i = tid; i <= L - n; i += HR_THREADS) {
+            bool same = true;
+            for (int j = 0; j < n - 1; ++j) same = same && h[i + j] == tail[j];
+            if (same) x[h[i + n - 1]] = -INFINITY;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- beam bookkeeping on the GPU
 // One HF 4.37 beam-search step's next-beam choice (cbw/generate.py BeamProcess.process; transformers
 // BeamSearchScorer.process): the B*k candidates beam_scores[r] + lp[r][j] (f64, the host's Python floats),
@@ -847,6 +905,17 @@ hipError_t cbw_greedy_select_launch(const float* logits, int B, int V, int ld, c
     if (B < 1 || B > 16 || V < 1 || ld < V) return hipErrorInvalidValue;
     hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, logits, V, ld, bias, bias_begin, ts_begin,
                        no_ts, eos, max_initial, ts_state, pos_rows, limit, active, tokens, logprob);
+    return hipGetLastError();
+}
+
+hipError_t cbw_history_rules_launch(float* logits, int B, int V, int ld, int* hist, int hist_ld, int* hist_len,
+                                    const int* last_tokens, const int* pos_rows, const int* active,
+                                    float repetition_penalty, int no_repeat_ngram_size, hipStream_t st) {
+    if (B < 1 || B > 16 || V < 1 || ld < V || hist_ld < 1 || hist_ld > CBW_HISTORY_MAX_LD ||
+        !(repetition_penalty > 0.f) || !(repetition_penalty < INFINITY) || no_repeat_ngram_size < 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(history_rules_kernel, dim3(B), dim3(HR_THREADS), 0, st, logits, V, ld, hist, hist_ld, hist_len,
+                       last_tokens, pos_rows, active, repetition_penalty, no_repeat_ngram_size);
     return hipGetLastError();
 }
 

@@ -48,6 +48,13 @@ def _dev_greedy() -> bool:
     return os.environ.get("CBW_DEV_GREEDY", "1") != "0"
 
 
+def _dev_history() -> bool:
+    """CBW_DEV_HISTORY, read at call time: greedy search under a caller's repetition_penalty / no_repeat_ngram_size
+    with both processors and the token choice on the GPU (DecoderEngine.greedy_dev over cbw_history_rules) instead of
+    the host loop over processed_step_fn; 0 switches it off."""
+    return os.environ.get("CBW_DEV_HISTORY", "1") != "0"
+
+
 def _dev_beam() -> bool:
     """CBW_DEV_BEAM, read at call time: beam search with the bookkeeping on the GPU (DecoderEngine.beam_search_dev /
     beam_search_windows) instead of the host scorer over step_fn; 0 switches it off."""
@@ -225,6 +232,13 @@ class PBAWhisper:
             # the token choice on the GPU, no host round trip per token (cbw_greedy_select; same result as `greedy`
             # below); the cross-attention K/V go through set_window, so no decoder.start
             return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin, rules)
+        if num_beams <= 1 and not free and len(prefix) >= 2 and _dev_history() and \
+                (c.get("repetition_penalty") is not None or c.get("no_repeat_ngram_size")):
+            # a caller's repetition_penalty / no_repeat_ngram_size on the GPU as well (cbw_history_rules in front of
+            # cbw_greedy_select; same result as `greedy` over processed_step_fn below, which beam search keeps)
+            return self.decoder.greedy_dev(enc_out, prefix, self.tokens.eot, max_length, bias, bias_begin, rules,
+                                           repetition_penalty=c.get("repetition_penalty"),
+                                           no_repeat_ngram_size=c.get("no_repeat_ngram_size") or 0)
         self.decoder.start(enc_out, rows)
         lp, nrs = c.get("length_penalty", 1.0), c.get("num_return_sequences", 1)
         # the host beam search every branch below runs, over that branch's step function

@@ -572,6 +572,32 @@ int cbw_sample_select(const float* logits, int B, int V, int ld, const float* bi
                       const int32_t* pos_rows, const int32_t* limit, int32_t* active, int32_t* tokens, float* logprob,
                       float temperature, int top_k, const float* noise, int64_t noise_ld, cbw_stream_t stream);
 
+/* The two logits processors that read a row's token history, for up to 16 rows on the GPU in front of
+ * cbw_greedy_select / cbw_sample_select, so a lock-step decode with repetition_penalty or no_repeat_ngram_size needs no
+ * host round trip per token (the kwargs pba_whisper.py:320-331 and :425-442 hand down to GenerationMixin.generate;
+ * transformers 4.37.2 _get_logits_processor puts RepetitionPenaltyLogitsProcessor, then NoRepeatNGramLogitsProcessor,
+ * in front of the suppression and timestamp processors, which are the select kernels' bias and rules).  Per row r with
+ * active[r] != 0, logits[r] (f32, row pitch ld) is rewritten in place from the row's history hist[r][0 .. hist_len[r])
+ * (int32 [B][hist_ld] and [B] on the device: the sequence so far, decoder prompt included; every token read from it is
+ * clamped into [0, V) before it indexes the logits):
+ *   upkeep -- the row's last token sits at position pos_rows[r].  hist_len[r] == pos_rows[r] + 1: the history is whole
+ *   (a slot just admitted, its prefix written by the caller; a reused slot needs nothing else).  hist_len[r] ==
+ *   pos_rows[r]: the row moved one position since the last call; last_tokens[r] is appended first and hist_len[r]
+ *   incremented.  Any other relation, or an append that cannot be made (last_tokens NULL, hist_len[r] == hist_ld),
+ *   leaves the row's logits and history untouched;
+ *   repetition_penalty p != 1 -- x[t] = x[t] < 0 ? x[t] * p : x[t] / p in fp32 (round to nearest), once per distinct
+ *   token t of the history however often it occurs (HF's gather, then scatter);
+ *   no_repeat_ngram_size n > 0 and hist_len + 1 >= n -- x[hist[i + n - 1]] = -inf for every i in [0, hist_len - n]
+ *   with hist[i .. i + n - 2] == the history's last n - 1 tokens (n == 1 bans every token of the history); after the
+ *   penalty: -inf wins.
+ * With p == 1 and n == 0 the call only keeps the history.  tokens, ts_state and active belong to the select kernels and
+ * are not written.  One workgroup per row over the row's history, no pass over V.  Does not allocate or synchronise.
+ * B in [1, 16], V >= 1, ld >= V, hist_ld in [1, 2048] (a workgroup stages its row's history in LDS),
+ * repetition_penalty > 0 and finite, no_repeat_ngram_size >= 0; last_tokens may be NULL. */
+int cbw_history_rules(float* logits, int B, int V, int ld, int32_t* hist, int hist_ld, int32_t* hist_len,
+                      const int32_t* last_tokens, const int32_t* pos_rows, const int32_t* active,
+                      float repetition_penalty, int no_repeat_ngram_size, cbw_stream_t stream);
+
 /* ---------------------------------------------------------------- building blocks (tests, tools)
  * NHWC bf16 implicit-GEMM convolution, y = act(conv(x, w) + bias (+ res)).
  * x [N][H][W][Cin], w [Cout][KH][KW][Cin], res/y [N][Ho][Wo][Cout]; Cin % 64 == 0, Cout % 64 == 0.

@@ -2,7 +2,10 @@
 one decode step per token (KV cache append, self + cross attention, MLP, vocabulary projection), against
 the step's HBM roofline (every decoder weight + the KV caches read once per step).
 usage: python tools/decode_bench.py [model] [beams] [steps]; DB_POS0=P: the timed steps start at position P (the
-keyword-prompted windows of C5 / e2e decode from ~150-230 prefix tokens: self-attention over several key chunks)"""
+keyword-prompted windows of C5 / e2e decode from ~150-230 prefix tokens: self-attention over several key chunks);
+DB_HISTORY=P,N (e.g. 1.3,3): also the lock-step greedy step of DB_ROWS rows (default 1; cbw_greedy_select +
+cbw_decoder_step_rows, as DecoderEngine.greedy_windows enqueues it) without and with the cbw_history_rules pre-pass at
+repetition_penalty P and no_repeat_ngram_size N, every row's history pos0 tokens long at the first timed step"""
 import os
 import sys
 import time
@@ -53,3 +56,59 @@ bytes_step = w_bytes + kv_bytes
 print(f"decoder {model} beams={beams} pos0={pos0} self_split={os.environ.get('CBW_DEC_SELF_SPLIT', '0')}: cross-KV {t_cross * 1e3:.2f} ms/window, step {t_step * 1e3:.3f} ms "
       f"({1 / t_step:.0f} steps/s, {beams / t_step:.0f} beam-tokens/s); {bytes_step / 1e9:.2f} GB/step -> "
       f"{bytes_step / t_step / 1e12:.2f} TB/s = {bytes_step / t_step / 8e12:.1%} of 8 TB/s")
+
+if os.environ.get("DB_HISTORY"):
+    from cbw import _lib  # noqa: E402
+    pen, ngram = os.environ["DB_HISTORY"].split(",")
+    pen, ngram = float(pen), int(ngram)
+    rows = int(os.environ.get("DB_ROWS", "1"))
+    lib, st = dec.lib, _lib.stream_handle()
+    prefix = [50258 + (i % 7) for i in range(max(2, pos0))]
+
+    def lock_step(history: bool) -> float:
+        """ms per step of select + decode step over ``rows`` one-row windows, the launches of _lock_step"""
+        dec.start_windows(rows, 1)
+        for s_ in range(rows):
+            dec.set_window(s_, enc[0])
+            dec.prefill_window(s_, 1, prefix)
+        ts_state = torch.tensor([[0, -1, -1, -1]] * rows, dtype=torch.int32, device=dev)
+        limit = torch.full((rows,), dec.max_len, dtype=torch.int32, device=dev)
+        active = torch.ones((rows,), dtype=torch.int32, device=dev)
+        log = torch.zeros((steps + 8, 2, rows), dtype=torch.int32, device=dev)
+        hist = torch.zeros((rows, dec.max_len + 1), dtype=torch.int32, device=dev)
+        hist[:, :len(prefix)] = torch.tensor(prefix, dtype=torch.int32)
+        hist_len = torch.full((rows,), len(prefix), dtype=torch.int32, device=dev)
+        last_pos = torch.zeros((rows,), dtype=torch.int32, device=dev)
+        lg = dec._logits.data_ptr()
+        no_eos = torch.zeros((V,), dtype=torch.float32, device=dev)   # EOS suppressed: the rows never end
+        no_eos[50257] = float("-inf")
+
+        def run(c0, c1):
+            for c in range(c0, c1):
+                if history:
+                    torch.sub(dec._posr, 1, out=last_pos)
+                    _lib.check(lib.cbw_history_rules(lg, rows, V, dec.vpad, hist.data_ptr(), hist.shape[1],
+                                                     hist_len.data_ptr(), log[c - 1, 0].data_ptr() if c else None,
+                                                     last_pos.data_ptr(), active.data_ptr(), pen, ngram, st),
+                               "cbw_history_rules")
+                _lib.check(lib.cbw_greedy_select(lg, rows, V, dec.vpad, no_eos.data_ptr(), no_eos.data_ptr(), -1, -1,
+                                                 50257, -1, ts_state.data_ptr(),
+                                                 dec._posr.data_ptr(), limit.data_ptr(), active.data_ptr(),
+                                                 log[c, 0].data_ptr(), log[c, 1].data_ptr(), st), "cbw_greedy_select")
+                dec.step_rows(log[c, 0])
+                dec._posr.add_(active)
+        run(0, 8)
+        torch.cuda.synchronize()
+        e0.record()
+        run(8, 8 + steps)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / steps
+
+    if rows > 16 or len(prefix) + steps + 8 >= dec.max_len:
+        sys.exit("DB_HISTORY: DB_ROWS <= 16 and pos0 + steps + 8 < max_len")
+    off = [lock_step(False) for _ in range(3)]
+    on = [lock_step(True) for _ in range(3)]
+    print(f"lock-step greedy step, {rows} rows, history from {len(prefix)} tokens: without the pre-pass "
+          f"{min(off):.4f} ms (three runs {' '.join(f'{v:.4f}' for v in off)}), with cbw_history_rules(p={pen}, n={ngram}) "
+          f"{min(on):.4f} ms ({' '.join(f'{v:.4f}' for v in on)}): +{(min(on) - min(off)) * 1e3:.1f} us")
